@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: RL-deconvolution throughput (Gvoxel*iterations/s) of the MI355X hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A step is one Richardson-Lucy iteration (forward blur + ratio, adjoint blur + update; decon.m:162-186) over
 the whole resident volume.  Workload at N = 1: BASELINE.json config C3 -- 2048 x 2048 x 512 fp32 volume,
@@ -9,6 +9,11 @@ the whole resident volume.  Workload at N = 1: BASELINE.json config C3 -- 2048 x
 regularize_interval = 0, stop_criterion = 0; synthetic seeded data already resident in HBM when the timed
 region starts.  At N > 1 the same volume is cut into N slabs along Y (one rank per GPU, RCCL halo exchange
 over xGMI twice per iteration) => strong scaling.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (its `roofline` is the whole-iteration figure of the
+timed steps).  --full adds everything that takes runs of its own: per-pass launch timings of the roofline, the edge taper /
+PCIe stages, the second rows, config 4 whole, decwrap.py end to end, the CPU baseline and the NCC metric (bench_ncc.py).
+--dump-outputs DIR writes a seeded sample of the deconvolved volume the last timed step left (dump_outputs).
 """
 from __future__ import annotations
 
@@ -30,6 +35,10 @@ WORKLOADS = {  # name: (volume (z,y,x), psf (z,y,x))
 }
 HBM_PEAK_GBS = 8000.0           # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level parameters)
 ALGO_BYTES_PER_VOXEL_ITER = 48  # RL FFT path, SURVEY.md section 8d / DESIGN.md
+DUMP_SAMPLES = 1 << 21          # --dump-outputs: voxels sampled from a larger volume (8 MB of float32)
+DUMP_WHOLE = 1 << 23            # ... a volume of at most this many voxels (32 MB) is written whole
+DUMP_PLANE = 2048               # ... the middle z plane, cropped about its centre to at most this extent in y and x
+DUMP_SEED = 2024
 
 
 def make_psf(kshape, gaussian=False):
@@ -56,6 +65,51 @@ def make_volume(shape, device, seed=1234):
     amp = torch.empty(nb, dtype=torch.float32, device=device).uniform_(0.2, 1.0, generator=g)
     vol.view(-1).index_put_((idx,), amp, accumulate=True)
     return vol
+
+
+def output_sample(vol, gshape, y0=0):
+    """What --dump-outputs writes, taken from the rows [y0, y0 + vol.shape[1]) of a (z, y, x) volume of global shape `gshape`
+    that one rank holds (the whole volume at N = 1).  Entries that lie in other ranks' rows are 0, so the arrays of all ranks
+    SUM to those of the whole volume.
+      deconvolved_sample      float32: the volume flattened when it has at most DUMP_WHOLE voxels, else the DUMP_SAMPLES voxels
+                              at numpy default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLES), sorted, duplicates dropped (the same
+                              flat indices in every run of a workload);
+      deconvolved_mid_plane   float32: the plane z = Z // 2, cropped about its centre to at most DUMP_PLANE x DUMP_PLANE;
+      deconvolved_plane_sums  float64: the sum of every z plane.
+    Returns torch tensors on the volume's device."""
+    import numpy as np
+    import torch
+    gz, gy, gx = gshape
+    y1 = y0 + vol.shape[1]
+    n = gz * gy * gx
+
+    def dev_index(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(vol.device)
+    idx = np.arange(n) if n <= DUMP_WHOLE else np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLES))
+    z, y, x = idx // (gy * gx), idx // gx % gy, idx % gx
+    mine = np.nonzero((y >= y0) & (y < y1))[0]
+    sample = torch.zeros(idx.size, dtype=torch.float32, device=vol.device)
+    if mine.size:
+        sample[dev_index(mine)] = vol[dev_index(z[mine]), dev_index(y[mine] - y0), dev_index(x[mine])]
+    cy, cx = min(gy, DUMP_PLANE), min(gx, DUMP_PLANE)
+    ya, xa = (gy - cy) // 2, (gx - cx) // 2
+    plane = torch.zeros((cy, cx), dtype=torch.float32, device=vol.device)
+    lo, hi = max(ya, y0), min(ya + cy, y1)
+    if lo < hi:
+        plane[lo - ya:hi - ya] = vol[gz // 2, lo - y0:hi - y0, xa:xa + cx]
+    sums = torch.empty(gz, dtype=torch.float64, device=vol.device)
+    zc = max(1, (64 << 20) // (vol.shape[1] * gx))   # planes per chunk: the float64 copy the sum makes stays within 512 MB
+    for z0 in range(0, gz, zc):
+        sums[z0:z0 + zc] = vol[z0:z0 + zc].sum(dim=(1, 2), dtype=torch.float64)
+    return {"deconvolved_sample": sample, "deconvolved_mid_plane": plane, "deconvolved_plane_sums": sums}
+
+
+def dump_outputs(out_dir, arrays):
+    """DIR/<name>.npy for every array of output_sample (float32 / float64, about 24 MB in all)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
 
 
 def pmc_traffic(pass_name, workload):
@@ -365,14 +419,21 @@ def main():
     ap.add_argument("--transport", default="rccl", choices=["rccl", "peer"],
                     help="halo exchange at N > 1: grouped send/recv of the process group (RCCL), or hipMemcpyPeerAsync into the "
                          "neighbour's buffers (copy engines; slab.PeerLink)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a seeded sample of the deconvolved volume as DIR/<name>.npy (output_sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline: per-pass roofline timings, block stages, second rows, c4 whole, "
+                         "decwrap end to end, the CPU baseline and the NCC metric (the --no-* options leave some of them out)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under a launcher: fan the ranks out as a child process tree before anything here touches the GPU
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
 
     ncc_workers = None
-    if args.gpus == 1 and not args.no_ncc and not args.no_cpu_baseline:
+    if args.full and args.gpus == 1 and not args.no_ncc and not args.no_cpu_baseline:
         import bench_ncc
         ncc_workers = bench_ncc.start_cpu_workers(host_cores())   # idle until the NCC CPU leg; started before the GPU is touched
 
@@ -467,6 +528,16 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        # before anything else runs on the volume (the per-pass timings of --full overwrite it)
+        arrays = output_sample(bl, vshape) if world == 1 else output_sample(drv.interior(), vshape, drv.y0)
+        if dist is not None:                         # every rank holds zeros outside its rows: the sum is the whole volume's
+            arrays = {k: a if args.backend == "nccl" else a.cpu() for k, a in arrays.items()}
+            for a in arrays.values():
+                dist.all_reduce(a, op=dist.ReduceOp.SUM)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, arrays)
+        del arrays
 
     if rank == 0:
         ms_per_step = elapsed * 1e3 / args.steps
@@ -476,7 +547,7 @@ def main():
         launch_vox = float(bl.numel())
         iteration_gbs = ALGO_BYTES_PER_VOXEL_ITER * local_vox / (dev_ms / args.steps * 1e-3) / 1e9
         roofline = None
-        if engine_used == 2:
+        if engine_used == 2 and args.full:
             try:
                 # per-pass launch durations, HIP events on the launch stream (mi_rl_time_pass); the dominant kernel
                 # is the one with the largest share of an iteration
@@ -521,7 +592,8 @@ def main():
         if roofline is None:
             roofline = {"bound": "hbm", "achieved": round(iteration_gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                         "frac": round(iteration_gbs / HBM_PEAK_GBS, 5), "traffic": None,
-                        "kernel": "rl_iteration (whole pipeline; no per-kernel hook on this engine)"}
+                        "kernel": "rl_iteration (whole pipeline; " + ("per-pass launch timings with --full)" if engine_used == 2 and not args.full
+                                                                       else "no per-kernel hook on this engine)")}
         roofline["iteration"] = {"algorithmic_bytes_per_voxel_iter": ALGO_BYTES_PER_VOXEL_ITER,
                                  "achieved_GBps": round(iteration_gbs, 2), "frac": round(iteration_gbs / HBM_PEAK_GBS, 5),
                                  "device_ms_per_iteration": round(dev_ms / args.steps, 4)}
@@ -535,7 +607,7 @@ def main():
                        "engine": {1: "direct", 2: "fft"}.get(engine_used, str(engine_used)), "parallelism": parallelism},
             "roofline": roofline,
         }
-        if world == 1 and not args.no_stages:
+        if args.full and world == 1 and not args.no_stages:
             ctx = bl = ratio = None                  # (the closures above see the rebinding: the context and its volume are freed)
             torch.cuda.empty_cache()
             capi.release_cached_memory()
@@ -560,12 +632,12 @@ def main():
                     out["decwrap_tiff"] = {"error": repr(e)}
                 torch.cuda.empty_cache()
                 capi.release_cached_memory()
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(vshape, kshape, gaussian=args.workload == "c1")
     ncc = None
     if world > 1:
         drv.close()                                  # (the copy-engine link: mapped peer memory, interprocess events)
-    if not args.no_ncc:
+    if args.full and not args.no_ncc:
         # second metric (BASELINE config 5).  N > 1: tile-row blocks, one block per rank (bench_ncc.py); every rank takes part
         if world > 1:
             step = drv = ctx = bl = None             # the slab context and its volume make room for the tile rows

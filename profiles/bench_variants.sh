@@ -1,4 +1,4 @@
-B="bench.py --steps 20 --warmup 5 --no-ncc --no-cpu-baseline"
+B="bench.py --full --steps 20 --warmup 5 --no-ncc --no-cpu-baseline"
 for rep in 1 2; do
 for v in "" "MI_X_DYN=1" "MI_X_DYN=1 MI_Z_DYN=1"; do
   echo "== $v" >> gpurun_out/r3_b2.txt

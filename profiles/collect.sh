@@ -7,7 +7,7 @@
 tag=${1:-r02}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 T="timeout -k 5 300"
-B="bench.py --steps 4 --warmup 1 --no-ncc --no-cpu-baseline --no-stages"
+B="bench.py --full --steps 4 --warmup 1 --no-ncc --no-cpu-baseline --no-stages"
 N="profiles/ncc_batch_probe.py 3"
 db() { ls gpurun_out/$1/*/*_results.db gpurun_out/$1/*_results.db 2>/dev/null | head -1; }
 $T rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$tag -o $tag -- python3 $B > gpurun_out/prof_$tag.log 2>&1
@@ -37,6 +37,6 @@ stats() {  # stats <name> <command...>: kernel statistics of a command -> gpurun
 }
 stats gauss python3 profiles/gauss_time.py
 stats edgetaper python3 profiles/edgetaper_slabs_probe.py
-stats direct_c2 python3 bench.py --workload c2 --engine direct --steps 3 --warmup 1 --no-ncc --no-cpu-baseline --no-stages
-stats direct_c1 python3 bench.py --workload c1 --engine direct --steps 20 --warmup 2 --no-ncc --no-cpu-baseline --no-stages
+stats direct_c2 python3 bench.py --full --workload c2 --engine direct --steps 3 --warmup 1 --no-ncc --no-cpu-baseline --no-stages
+stats direct_c1 python3 bench.py --full --workload c1 --engine direct --steps 20 --warmup 2 --no-ncc --no-cpu-baseline --no-stages
 echo "small passes done"

@@ -4,7 +4,7 @@
 tag=${1:-r05}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 T="timeout -k 5 400"
-B="bench.py --steps 20 --warmup 2 --no-ncc --no-cpu-baseline --no-stages"
+B="bench.py --full --steps 20 --warmup 2 --no-ncc --no-cpu-baseline --no-stages"
 db() { ls gpurun_out/$1/*/*_results.db gpurun_out/$1/*_results.db 2>/dev/null | head -1; }
 export MI_FFT_PLACE_LOG=1
 # (1) the headline loop unprofiled, then under the kernel trace: the same command, two processes
@@ -13,7 +13,7 @@ $T rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$tag -o $tag -- python3 $
 python3 profiles/summarize.py "$(db prof_$tag)" gpurun_out/${tag}_bench_c3_kernel_stats.csv
 echo "bench kernel stats done"
 unset MI_FFT_PLACE_LOG
-B4="bench.py --steps 4 --warmup 1 --no-ncc --no-cpu-baseline --no-stages"
+B4="bench.py --full --steps 4 --warmup 1 --no-ncc --no-cpu-baseline --no-stages"
 $T rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_F -o pmc -- python3 $B4 > gpurun_out/pmc_F.log 2>&1
 $T rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_W -o pmc -- python3 $B4 > gpurun_out/pmc_W.log 2>&1
 python3 profiles/pmc_summary.py gpurun_out/pmc_F gpurun_out/pmc_W gpurun_out/${tag}_pmc_traffic.json > gpurun_out/${tag}_pmc_traffic.txt
@@ -42,8 +42,8 @@ stats() {  # stats <name> <command...>
   rm -rf gpurun_out/prof_x
 }
 stats c4_rank python3 profiles/shape_time.py 1024 576 4096 127 63 63
-stats c4_whole python3 bench.py --workload c4 --steps 3 --warmup 1 --no-ncc --no-cpu-baseline --no-stages
+stats c4_whole python3 bench.py --full --workload c4 --steps 3 --warmup 1 --no-ncc --no-cpu-baseline --no-stages
 stats gauss python3 profiles/gauss_time.py
-stats direct_c2 python3 bench.py --workload c2 --engine direct --steps 3 --warmup 1 --no-ncc --no-cpu-baseline --no-stages
-stats direct_c1 python3 bench.py --workload c1 --engine direct --steps 20 --warmup 2 --no-ncc --no-cpu-baseline --no-stages
+stats direct_c2 python3 bench.py --full --workload c2 --engine direct --steps 3 --warmup 1 --no-ncc --no-cpu-baseline --no-stages
+stats direct_c1 python3 bench.py --full --workload c1 --engine direct --steps 20 --warmup 2 --no-ncc --no-cpu-baseline --no-stages
 echo "all done"

@@ -4,7 +4,7 @@
 # TCC cycles) (four TCC counters are what one pass collects).   bash profiles/ea_probe.sh <out.txt> [processes]
 out=$1; n=${2:-5}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-B="bench.py --steps 4 --warmup 1 --no-ncc --no-cpu-baseline --no-stages"
+B="bench.py --full --steps 4 --warmup 1 --no-ncc --no-cpu-baseline --no-stages"
 : > "$out"
 for i in $(seq 1 $n); do
   timeout -k 5 90 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_LEVEL_sum --kernel-trace --output-format csv -d gpurun_out/ea_$i -o ea -- python3 $B > gpurun_out/ea_$i.log 2>&1

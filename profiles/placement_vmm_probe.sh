@@ -3,7 +3,7 @@
 # MI_FFT_VMM=<order>[,<chunk MB>]) against the plain allocation; every line is a fresh process.
 #   bash profiles/placement_vmm_probe.sh > gpurun_out/r04_placement_vmm.txt
 cd "$GRAFT_REPO_ROOT" || exit 1
-B="bench.py --steps 20 --warmup 5 --no-ncc --no-cpu-baseline --no-stages"
+B="bench.py --full --steps 20 --warmup 5 --no-ncc --no-cpu-baseline --no-stages"
 run() {
   env MI_IPP_PROBES=1 "$@" timeout -k 5 150 python3 $B 2>gpurun_out/vmm.err | python3 -c "
 import sys, json

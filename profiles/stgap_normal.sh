@@ -5,7 +5,7 @@ for round in 1 2; do
 for g in default 128 4224 65664 1048704 5242880 2097152; do
   echo -n "gap $g: "
   if [ "$g" = default ]; then unset MI_FFT_STGAP; else export MI_FFT_STGAP=$g; fi
-  python3 bench.py --steps 10 --warmup 3 --no-ncc --no-cpu-baseline --no-stages 2>/dev/null | python3 -c "
+  python3 bench.py --full --steps 10 --warmup 3 --no-ncc --no-cpu-baseline --no-stages 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
