@@ -18,6 +18,7 @@ IPC_HANDLE_BYTES = 64  # MI_IPC_HANDLE_BYTES
 BOUNDARY_ZERO, BOUNDARY_REPLICATE, BOUNDARY_CIRCULAR = 0, 1, 2
 ENGINE_AUTO, ENGINE_DIRECT, ENGINE_FFT = 0, 1, 2
 NORTH_SOUTH, WEST_EAST = 0, 1
+SINBLEND, NOBLEND = 0, 1   # mi_blending (include/mi_stitch.h)
 
 
 MI_ERR_INVALID, MI_ERR_HIP, MI_ERR_FFT, MI_ERR_NOMEM, MI_ERR_UNSUPPORTED = -1, -2, -3, -4, -5  # include/mi_common.h
@@ -132,6 +133,9 @@ SIGNATURES = {
     "mi_peer_link_status": (_i, [_vp, C.POINTER(_i)]),
     "mi_peer_link_disconnect": (_i, [_vp]),
     "mi_peer_link_destroy": (_i, [_vp]),
+    # mi_stitch.h
+    "mi_merge_volume_dims": (_i, [_i, _i, _ip, _ip, _ip, _i, _i, _i, _ip]),
+    "mi_merge_slab": (_i, [_i, _vp, _i, _i, _ip, _ip, _ip, _i, _i, _i, C.POINTER(_vp), _i, _i] + [_i] * 6 + [_vp]),
     # mi_crossmips.h
     "mi_ncc_default_params": (None, [_i, _i, _i, C.POINTER(NccParams)]),
     "mi_ncc_mips": (_i, [_i, _vp, _vp, _vp] + [_i] * 10 + [C.POINTER(NccParams), C.POINTER(NccDescr)]),

@@ -29,10 +29,19 @@ geometry of the project (``ipp_amd.tsproject``), and the output is the same proj
 Step 3 combines the per-layer records of every pair into the most reliable one per direction
 (StackStitcher::projectDisplacements, Displacement::projectDisplacements, DisplacementMIPNCC::combine); step 4 resets the
 directions whose reliability is below the threshold to the stage displacement and flags the stitchable stacks
-(StackStitcher::thresholdDisplacements).  Both are host-side bookkeeping on the XML (SURVEY.md 8f item 3).  Steps 1 and 5
-(import, global placement + merge) and the interactive pipeline around them stay with the reference's tools.
+(StackStitcher::thresholdDisplacements).  Both are host-side bookkeeping on the XML (SURVEY.md 8f item 3).
+
+Steps 5 and 6 are drop-ins for ``terastitcher -5 / -6`` (project files only):
+
+    python process_images.py -5 --projin xml_import_step_4.xml --projout xml_merging.xml [--algorithm MST]
+    python process_images.py -6 --projin xml_merging.xml --volout OUT --volout_plugin "TiledXY|2Dseries"
+                                [--slicewidth W --sliceheight H --D0 z0 --D1 z1 --algorithm SINBLEND|NOBLEND] [--resolutions 0]
+
+Step 5 is the MST placement (TPAlgoMST::execute, host); step 6 merges the placed stacks on the device (include/mi_stitch.h) and
+writes the reference's RES(VxHxD)/V/V_H/V_H_D.tif tree at resolution 0.  Step 1 (import) and the interactive pipeline around
+the steps stay with the reference's tools.
 With ``torchrun`` the pairs of a layer are dealt round-robin to the ranks (no collective; the per-rank XML fragments
-are merged by rank 0, like Parastitcher's mergedisplacements).
+are merged by rank 0, like Parastitcher's mergedisplacements); under step 6 each rank writes a contiguous range of output slices.
 """
 from __future__ import annotations
 
@@ -63,6 +72,16 @@ def build_parser():
     p.add_argument("--subvoldim", type=int, default=200, help="slices per z-layer (S_config.h:60)")
     p.add_argument("--threshold", type=float, default=0.65, help="reliability threshold recorded for step 4")
     p.add_argument("--projout", type=Path, default=None, help="output XML (default <input>/xml_displcomp.xml)")
+    p.add_argument("-5", "--placetiles", dest="step5", action="store_true", help="step 5: global tile placement (MST)")
+    p.add_argument("-6", "--merge", dest="step6", action="store_true", help="step 6: merge of the placed tiles (GPU)")
+    p.add_argument("--algorithm", default=None, help="step 5: MST (default); step 6: SINBLEND (default) or NOBLEND")
+    p.add_argument("--volout", type=Path, default=None, help="step 6: output folder")
+    p.add_argument("--volout_plugin", default="TiledXY|2Dseries", help="step 6: output format (TiledXY|2Dseries only)")
+    p.add_argument("--slicewidth", type=int, default=-1, help="step 6: output tile width (default: the whole volume)")
+    p.add_argument("--sliceheight", type=int, default=-1, help="step 6: output tile height (default: the whole volume)")
+    p.add_argument("--D0", type=int, default=-1, help="step 6: first output slice")
+    p.add_argument("--D1", type=int, default=-1, help="step 6: last output slice (included, as terastitcher's --D1)")
+    p.add_argument("--resolutions", default="0", help="step 6: output resolutions (only 0 is built)")
     return p
 
 
@@ -235,8 +254,74 @@ def project_steps(args):
     return 0
 
 
+def step5_place(args):
+    """terastitcher -5: ABS_V/H/D from the thresholded displacements (tsproject.Project.computeTilesPlacement)."""
+    from ipp_amd import tsproject
+    algorithm = args.algorithm or "MST"
+    if algorithm not in tsproject.PLACEMENT_ALGORITHMS:
+        raise SystemExit(f"-5: tiles placement algorithm \"{algorithm}\" is not built: only MST (LQP, SCANV and SCANH stay with "
+                         "the reference's terastitcher -5)")
+    if not _is_project(args.projin):
+        raise SystemExit("-5 needs --projin PROJECT.xml, a TeraStitcher project after step 4: the tile_<row>_<col>.npy mode "
+                         "has no stage positions to place")
+    if args.projout is None:
+        raise SystemExit("-5 needs --projout")
+    proj = tsproject.Project.load(args.projin)
+    proj.computeTilesPlacement(algorithm)
+    proj.save(args.projout)
+    print(f"wrote {args.projout}")
+    return 0
+
+
+def step6_merge(args):
+    """terastitcher -6 at resolution 0: the stitched volume as a TiledXY|2Dseries TIFF tree (ipp_amd.merge, GPU).  Under torchrun
+    every rank writes a contiguous share of the output slices (no collective: the ranks' files never collide)."""
+    from ipp_amd import merge, tsproject
+    blending = args.algorithm or "SINBLEND"
+    if blending not in merge.BLENDINGS:
+        raise SystemExit(f"-6: blending \"{blending}\" is not built: SINBLEND or NOBLEND")
+    if args.volout_plugin != "TiledXY|2Dseries":
+        raise SystemExit(f"-6: output format \"{args.volout_plugin}\" is not built: TiledXY|2Dseries only")
+    res = [r for r in re.split(r"[,\s]+", str(args.resolutions).strip()) if r]
+    if res != ["0"]:
+        raise SystemExit(f"-6: --resolutions {args.resolutions}: only resolution 0 is built (no halving pyramid)")
+    if not _is_project(args.projin):
+        raise SystemExit("-6 needs --projin PROJECT.xml, a TeraStitcher project after step 5: the tile_<row>_<col>.npy mode is "
+                         "not merged")
+    if args.volout is None:
+        raise SystemExit("-6 needs --volout")
+    import torch
+    from ipp_amd import capi
+    capi.require_gpu()
+    proj = tsproject.Project.load(args.projin)
+    geo = merge.geometry(proj)
+    depth, V, H = geo.shape
+    sh = V if args.sliceheight == -1 else args.sliceheight
+    sw = H if args.slicewidth == -1 else args.slicewidth
+    try:
+        merge.check_slice_dims(sh if args.sliceheight != -1 else merge.TMITREE_MIN_BLOCK_DIM,
+                               sw if args.slicewidth != -1 else merge.TMITREE_MIN_BLOCK_DIM)
+    except ValueError as e:
+        raise SystemExit(f"-6: {e}")
+    D0 = 0 if args.D0 < 0 else args.D0
+    D1 = depth if args.D1 < 0 or args.D1 + 1 > depth else args.D1 + 1     # --D1 is the last slice (ui/main.cpp:412)
+    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    torch.cuda.set_device(dev)
+    n = D1 - D0
+    a = D0 + (n * rank) // world
+    b = D0 + (n * (rank + 1)) // world
+    made = merge.merge_tiles(proj, args.volout, sh, sw, D0, D1, blending, dev, out_D0=a, out_D1=b)
+    print(f"rank {rank}: wrote {made} slices of output slices [{a},{b}) to {args.volout}")
+    return 0
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.step5:
+        return step5_place(args)
+    if args.step6:
+        return step6_merge(args)
     if (args.step2 or args.step3 or args.step4) and _is_project(args.projin):
         return project_steps(args)
     if args.input is None:

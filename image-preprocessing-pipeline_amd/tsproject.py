@@ -10,6 +10,7 @@ computation itself is ``crossmips.compute_displacements`` (GPU).
   computeDisplacements           StackStitcher::computeDisplacements (StackStitcher.cpp:128-400): z layers, pair loop
   projectDisplacements           StackStitcher::projectDisplacements (StackStitcher.cpp:1563-1624)
   thresholdDisplacements         StackStitcher::thresholdDisplacements (StackStitcher.cpp:1626-1720)
+  computeTilesPlacement          StackStitcher::computeTilesPlacement -> TPAlgoMST::execute (TPAlgoMST.cpp:66-250), step 5
 
 Numbers are written the way TinyXML writes them: integers with %d, doubles with %g (tinyxml.cpp:1216-1225), so reliabilities
 and NCC peaks carry six significant digits from one step's file to the next, exactly as between the reference's own steps.
@@ -32,6 +33,8 @@ from .crossmips import (DisplacementMIPNCC, S_DISPL_SEARCH_RADIUS_DEF, S_SUBVOL_
 
 FORMAT_ID = "TiledXY|2Dseries"      # vmStackedVolume.cpp:96
 S_OVERLAP_MIN = 1                   # S_config.h
+S_UNRELIABLE_WEIGHT = 1000          # S_config.h:89
+PLACEMENT_ALGORITHMS = ("MST",)     # TPAlgo::instanceAlgorithm; LQP / SCANV / SCANH are not built
 _SIDES = ("NORTH", "EAST", "SOUTH", "WEST")
 
 
@@ -400,6 +403,90 @@ class Project:
                 self.insertDisplacement(self.STACKS[r][c], self.STACKS[rb][cb], d)
                 n += 1
         return n
+
+    def computeTilesPlacement(self, algorithm: str = "MST"):
+        """Step 5: ABS_V / ABS_H / ABS_D of every stack from the thresholded displacements (TPAlgoMST::execute).
+
+        One shortest-path tree per direction from the stitchable stack nearest to the top-left corner; an edge weighs
+        SAFE_DIVIDE(1, reliability, S_UNRELIABLE_WEIGHT) in float.  The relaxation runs in the reference's loop order with a
+        strict ``<`` on float sums, so ties and unreliable links resolve as there; the coordinates are the displacements summed
+        along the predecessor chain, then translated so that stack [0,0] is at the origin."""
+        if algorithm not in PLACEMENT_ALGORITHMS:
+            raise ValueError(f"tiles placement algorithm \"{algorithm}\" is not supported: only MST is built "
+                             "(LQP, SCANV and SCANH stay with the reference's terastitcher -5)")
+        R, C = self.N_ROWS, self.N_COLS
+        S = self.STACKS
+        f32 = np.float32
+        for i in range(R):
+            for j in range(C):
+                for side, present in (("SOUTH", i < R - 1), ("EAST", j < C - 1), ("NORTH", i > 0), ("WEST", j > 0)):
+                    if present and len(getattr(S[i][j], side)) != 1:
+                        raise ValueError(f"in TPAlgoMST::execute(): stack [{i},{j}] MUST contain one displacement only at {side} "
+                                         "(run steps 3 and 4 first)")
+        # 0) source: the stitchable stack nearest to the top-left corner (float distances, strict <)
+        src, best = (0, 0), f32(np.inf)
+        for i in range(R):
+            for j in range(C):
+                d = np.sqrt(f32(i * i + j * j), dtype=np.float32)
+                if S[i][j].stitchable and d < best:
+                    src, best = (i, j), d
+
+        def weight(disp, k):
+            rel = f32(disp.getReliability(k))
+            return f32(S_UNRELIABLE_WEIGHT) if rel == 0 else f32(1) / rel
+        # 1-2) distances and predecessors, relaxed |V| times in the reference's order
+        inf = f32(np.inf)
+        D = [[[inf] * 3 for _ in range(C)] for _ in range(R)]
+        pred = [[[None] * 3 for _ in range(C)] for _ in range(R)]
+        D[src[0]][src[1]] = [f32(0)] * 3
+        wS = [[[weight(S[i][j].SOUTH[0], k) for k in range(3)] if i < R - 1 else None for j in range(C)] for i in range(R)]
+        wE = [[[weight(S[i][j].EAST[0], k) for k in range(3)] if j < C - 1 else None for j in range(C)] for i in range(R)]
+        for _ in range(R * C):
+            for i in range(R):
+                for j in range(C):
+                    for k in range(3):
+                        if i != R - 1:
+                            w = wS[i][j][k]
+                            if f32(D[i][j][k] + w) < D[i + 1][j][k]:
+                                D[i + 1][j][k] = f32(D[i][j][k] + w)
+                                pred[i + 1][j][k] = (i, j)
+                            if f32(D[i + 1][j][k] + w) < D[i][j][k]:
+                                D[i][j][k] = f32(D[i + 1][j][k] + w)
+                                pred[i][j][k] = (i + 1, j)
+                        if j != C - 1:
+                            w = wE[i][j][k]
+                            if f32(D[i][j][k] + w) < D[i][j + 1][k]:
+                                D[i][j + 1][k] = f32(D[i][j][k] + w)
+                                pred[i][j + 1][k] = (i, j)
+                            if f32(D[i][j + 1][k] + w) < D[i][j][k]:
+                                D[i][j][k] = f32(D[i][j + 1][k] + w)
+                                pred[i][j][k] = (i, j + 1)
+
+        def displacement(u, v):
+            """u->getDisplacement(v) (vmVirtualStack.h:132-154): u's record on the side where v lies."""
+            (ur, uc), (vr, vc) = u, v
+            side = {(-1, 0): "NORTH", (0, -1): "WEST", (1, 0): "SOUTH", (0, 1): "EAST"}[(vr - ur, vc - uc)]
+            return getattr(S[ur][uc], side)[0]
+        # 3-4) absolute coordinates along the predecessor chains
+        absc = [[[0, 0, 0] for _ in range(C)] for _ in range(R)]
+        for i in range(R):
+            for j in range(C):
+                if (i, j) == src:
+                    continue
+                for k in range(3):
+                    v, n = (i, j), 0
+                    while v != src:
+                        u = pred[v[0]][v[1]][k]
+                        if u is None or n > R * C:
+                            raise ValueError("...in TPAlgoMST::execute(): error in the predecessor matrix")
+                        absc[i][j][k] += int(displacement(u, v).VHD_coords[k])
+                        v, n = u, n + 1
+        # 5) stack [0,0] at the origin
+        t = list(absc[0][0])
+        for i in range(R):
+            for j in range(C):
+                S[i][j].ABS_V, S[i][j].ABS_H, S[i][j].ABS_D = (absc[i][j][k] - t[k] for k in range(3))
+        return src
 
     def mergeDisplacements(self, other: "Project"):
         """mergedisplacements (Parastitcher.py:474-508): the displacement lists of another partial result are appended."""
