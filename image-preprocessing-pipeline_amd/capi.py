@@ -19,6 +19,7 @@ BOUNDARY_ZERO, BOUNDARY_REPLICATE, BOUNDARY_CIRCULAR = 0, 1, 2
 ENGINE_AUTO, ENGINE_DIRECT, ENGINE_FFT = 0, 1, 2
 NORTH_SOUTH, WEST_EAST = 0, 1
 SINBLEND, NOBLEND = 0, 1   # mi_blending (include/mi_stitch.h)
+HALVE_MEAN, HALVE_MAX = 0, 1   # mi_halve_method (include/mi_pyramid.h)
 
 
 MI_ERR_INVALID, MI_ERR_HIP, MI_ERR_FFT, MI_ERR_NOMEM, MI_ERR_UNSUPPORTED = -1, -2, -3, -4, -5  # include/mi_common.h
@@ -136,6 +137,11 @@ SIGNATURES = {
     # mi_stitch.h
     "mi_merge_volume_dims": (_i, [_i, _i, _ip, _ip, _ip, _i, _i, _i, _ip]),
     "mi_merge_slab": (_i, [_i, _vp, _i, _i, _ip, _ip, _ip, _i, _i, _i, C.POINTER(_vp), _i, _i] + [_i] * 6 + [_vp]),
+    # mi_pyramid.h
+    "mi_pyramid_slab": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _ip, C.POINTER(_vp)]),
+    "mi_tiff3d_write_blocks": (_i, [_i, C.POINTER(C.c_char_p), C.POINTER(_vp), C.POINTER(C.c_int64), _ip, _ip, _ip, _i, _i, _i, _i,
+                                    _i]),
+    "mi_tiff_lzw_encode": (_i, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64)]),
     # mi_crossmips.h
     "mi_ncc_default_params": (None, [_i, _i, _i, C.POINTER(NccParams)]),
     "mi_ncc_mips": (_i, [_i, _vp, _vp, _vp] + [_i] * 10 + [C.POINTER(NccParams), C.POINTER(NccDescr)]),

@@ -1,0 +1,390 @@
+"""The TeraFly conversion: a folder of 2-D TIFF slices to the multi-resolution "TIFF (tiled, 3D)" tree that Vaa3D / TeraFly open.
+
+    convert(src, dst, resolutions="012345", halve="mean", ...)
+
+restates ``teraconverter --sfmt="TIFF (series, 2D)" --dfmt="TIFF (tiled, 3D)"`` (VolumeConverter::generateTilesVaa3DRaw,
+VolumeConverter.cpp:1840-2520) for single-channel 8- and 16-bit series:
+
+    <dst>/RES(<V>x<H>x<D>)/<V0>/<V0>_<H0>/<V0>_<H0>_<D0>.tif       one multi-page TIFF per block, LZW, RowsPerStrip 1
+    <dst>/RES(<V>x<H>x<D>)/mdata.bin                               TiledVolume::save of the level
+
+The volume is walked in z-groups of ``z_max_res = max(min(64, block_depth / 2), 2^halve_pow2[last])`` slices; each group is halved
+on its own (``mi_pyramid_slab``, include/mi_pyramid.h), so a group loses its odd last slice at every 3-D level -- why
+RES(...x9) of 37 slices holds 8 pages.  The level names still say ``depth / 2^h``.  A group's slices go to the device in row
+bands sized from the free device memory (band heights are multiples of 2^deepest level, so the bands halve as the whole plane
+does); each level's pages are appended to their block files (``mi_tiff3d_write_blocks``, LZW on a host thread pool) as soon as
+the group is done, as appendSlice2Tiff3DFile does.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import os
+import struct
+from dataclasses import dataclass, field
+from pathlib import Path
+
+import numpy as np
+
+STANDARD_BLOCK_DEPTH = 64        # IM_config.h
+TMITREE_MIN_BLOCK_DIM = 250      # IM_config.h:151
+MAX_LEVELS = 10                  # S_MAX_MULTIRES: the levels --resolutions can name
+HALVE = {"mean": 0, "max": 1}    # mi_halve_method
+
+
+def _tiles(total, block, fixed):
+    """Block sizes along one axis: ``ceil(total / block)`` blocks as uniform as possible, or (fixed tiling) ``block`` each and a
+    smaller last one (VolumeConverter.cpp:1925-1955)."""
+    n = int(math.ceil(total / np.float32(block)))
+    if fixed:
+        return [block if k < n - 1 else (block if total % block == 0 else total % block) for k in range(n)]
+    return [total // n + (1 if k < total % n else 0) for k in range(n)]
+
+
+def _name6(v):
+    return str(int(v)).rjust(6, "0")
+
+
+@dataclass
+class Plan:
+    """Every decision of the conversion that does not depend on voxel values."""
+    depth: int
+    height: int
+    width: int
+    V0: int
+    H0: int
+    D0: int
+    selected: list
+    hp: list                 # halve_pow2[i]: D is halved 2^hp[i] times at level i
+    rows: list               # rows[i]: block heights at level i
+    cols: list
+    deps: list               # deps[i]: nominal block depths at level i
+    z_max_res: int
+    bytes: int = 2
+    n_res: int = field(init=False)
+
+    def __post_init__(self):
+        self.n_res = len(self.hp)
+
+    def level_shape(self, i):
+        return self.depth // 2 ** self.hp[i], self.height // 2 ** i, self.width // 2 ** i
+
+    def res_dir(self, i):
+        d, v, h = self.level_shape(i)
+        return f"RES({v}x{h}x{d})"
+
+    def v_name(self, i, r0):
+        return _name6((self.V0 + r0 * 2 ** i) * 10)
+
+    def h_name(self, i, c0):
+        return _name6((self.H0 + c0 * 2 ** i) * 10)
+
+    def d_name(self, i, s):
+        return _name6(self.D0 * 10 + 2 ** self.hp[i] * s * 10)
+
+    def blocks(self, i):
+        """[(row start, rows, col start, cols, "V/V_H")] of level i."""
+        out, r0 = [], 0
+        for nr in self.rows[i]:
+            c0 = 0
+            for nc in self.cols[i]:
+                vn, hn = self.v_name(i, r0), self.h_name(i, c0)
+                out.append((r0, nr, c0, nc, f"{vn}/{vn}_{hn}"))
+                c0 += nc
+            r0 += nr
+        return out
+
+    def groups(self):
+        """[(z, z_size)]: the z-groups, relative to D0 (z_size of the leftover group = depth % z_max_res)."""
+        z_ratio = self.depth // self.z_max_res
+        return [(z, self.z_max_res if g + 1 <= z_ratio else self.depth % self.z_max_res)
+                for g, z in enumerate(range(0, self.depth, self.z_max_res))]
+
+    def appends(self):
+        """Per group, per selected level: [(level, D-block index, first group page, pages)] -- the reference's block walk
+        (stack_block / slice_start / slice_end, one block change at most per group)."""
+        blk = [0] * self.n_res
+        s_end = [self.deps[i][0] - 1 for i in range(self.n_res)]
+        out = []
+        for z, z_size in self.groups():
+            g = []
+            for i in range(self.n_res):
+                h = 2 ** self.hp[i]
+                if z // h > s_end[i]:
+                    blk[i] += 1
+                    s_end[i] += self.deps[i][blk[i]] if blk[i] < len(self.deps[i]) else 0
+                n = z_size // h
+                if not self.selected[i] or n <= 0:
+                    continue
+                split = n
+                for bz in range(n):
+                    if z // h + bz > s_end[i]:
+                        split = bz
+                        break
+                if split > 0:
+                    g.append((i, blk[i], 0, split))
+                if split < n:
+                    g.append((i, blk[i] + 1, split, n - split))
+            out.append(g)
+        return out
+
+    def d_block_start(self, i, k):
+        return sum(self.deps[i][:k])
+
+
+def plan(shape, resolutions="0", block=(-1, -1, -1), isotropic=False, fixed_tiling=False, sub=(-1, -1, -1, -1, -1, -1),
+         bytes_per_sample=2) -> Plan:
+    """The plan of a series of ``shape`` = (D, V, H) slices; ``block`` = (--height, --width, --depth), -1 = the whole extent;
+    ``sub`` = (--V0, --V1, --H0, --H1, --D0, --D1), -1 = unset (D1 / V1 / H1 excluded)."""
+    D, V, H = shape
+    V0, V1, H0, H1, D0, D1 = sub
+    V0 = max(V0, 0)
+    H0 = max(H0, 0)
+    D0 = max(D0, 0)
+    V1 = V if V1 < 0 or V1 > V else V1
+    H1 = H if H1 < 0 or H1 > H else H1
+    D1 = D if D1 < 0 or D1 > D else D1
+    if V0 >= V1 or H0 >= H1 or D0 >= D1:
+        raise ValueError(f"empty subvolume [{V0},{V1}) x [{H0},{H1}) x [{D0},{D1}) of a {V} x {H} x {D} series")
+    height, width, depth = V1 - V0, H1 - H0, D1 - D0
+    bh, bw, bd = (height if block[0] < 0 else block[0], width if block[1] < 0 else block[1], depth if block[2] < 0 else block[2])
+    if bh < TMITREE_MIN_BLOCK_DIM or bw < TMITREE_MIN_BLOCK_DIM:
+        raise ValueError(f"blocks of {bh} x {bw}: the minimum dimension for block height and width is {TMITREE_MIN_BLOCK_DIM} "
+                         "(VolumeConverter::generateTilesVaa3DRaw)")
+    if bd <= 0:
+        raise ValueError(f"block depth {bd}")
+    selected = [str(i) in str(resolutions) for i in range(MAX_LEVELS)]
+    if not any(selected):
+        raise ValueError(f"--resolutions={resolutions!r} selects no level (digits 0..{MAX_LEVELS - 1})")
+    n_res = max(i + 1 for i in range(MAX_LEVELS) if selected[i])
+    if isotropic:
+        # a 2-D series has unit voxels (SimpleVolume): D is halved whenever VXL_D <= 2 max(VXL_V, VXL_H) at that level
+        hp = [0] * n_res
+        vx2, hx2, vd = np.float32(2), np.float32(2), np.float32(1)
+        for i in range(1, n_res):
+            hp[i] = hp[i - 1]
+            if vd <= max(vx2, hx2):
+                hp[i] += 1
+                vd *= 2
+            vx2 *= 2
+            hx2 *= 2
+    else:
+        hp = list(range(n_res))
+    rows = [_tiles(height // 2 ** i, bh, fixed_tiling) for i in range(n_res)]
+    cols = [_tiles(width // 2 ** i, bw, fixed_tiling) for i in range(n_res)]
+    deps = []
+    for i in range(n_res):
+        t = depth // 2 ** hp[i]
+        n = int(math.ceil(t / np.float32(bd)))
+        if fixed_tiling:   # the reference sizes the last block from depth / 2^i whatever halve_pow2 says (VolumeConverter.cpp:1930)
+            last = depth // 2 ** i
+            deps.append([bd if k < n - 1 else (bd if last % bd == 0 else last % bd) for k in range(n)])
+        else:
+            deps.append([t // n + (1 if k < t % n else 0) for k in range(n)])
+    for i in range(n_res):
+        if min(height // 2 ** i, width // 2 ** i) <= 0 or not deps[i]:
+            raise ValueError(f"level {i} of a {height} x {width} x {depth} volume is empty")
+    z_max_res = max(min(STANDARD_BLOCK_DEPTH, bd // 2), 2 ** hp[n_res - 1])
+    if z_max_res > 1 and z_max_res > bd // 2:
+        raise ValueError(f"too much resolutions({n_res}): too much slices ({z_max_res}) in the buffer "
+                         f"(block depth {bd}: VolumeConverter::generateTilesVaa3DRaw)")
+    return Plan(depth, height, width, V0, H0, D0, selected, hp, rows, cols, deps, z_max_res, bytes_per_sample)
+
+
+def mdata_bytes(p: Plan, i: int) -> bytes:
+    """RES(...)/mdata.bin of level i (TiledVolume::save + Block::binarizeInto; MDATA_BIN_FILE_VERSION 2, reference system
+    {1,2,3}, voxels 2^i x 2^i x 2^hp[i] um, origin from the first block's file name in 0.1 um / 1e4)."""
+    written = {k for g in p.appends() for (lv, k, _, _) in g if lv == i}
+    dblocks = sorted(written)
+    bl = p.blocks(i)
+    nrows, ncols = len(p.rows[i]), len(p.cols[i])
+    first_d = p.d_name(i, p.d_block_start(i, dblocks[0]))
+    org = [np.float32(np.float32(int(v)) / np.float32(10000.0)) for v in (p.v_name(i, 0), p.h_name(i, 0), first_d)]
+    sv, sd = float(2 ** i), float(2 ** p.hp[i])
+    dim_d = sum(p.deps[i][k] for k in dblocks)
+    b = struct.pack("<f3i", 2.0, 1, 2, 3) + struct.pack("<6f", sv, sv, sd, sv, sv, sd) + struct.pack("<3f", *org)
+    b += struct.pack("<3I2H", sum(p.rows[i]), sum(p.cols[i]), dim_d, nrows, ncols)
+    for r0, nr, c0, nc, dirname in bl:
+        vh = dirname.split("/")[1]
+        b += struct.pack("<5I2i", nr, nc, dim_d, len(dblocks), 1, r0, c0)
+        b += struct.pack("<H", len(dirname) + 1) + dirname.encode() + b"\0"
+        absd = 0
+        for k in dblocks:
+            f = f"{vh}_{p.d_name(i, p.d_block_start(i, k))}.tif"
+            b += struct.pack("<H", len(f) + 1) + f.encode() + b"\0" + struct.pack("<Ii", p.deps[i][k], absd)
+            absd += p.deps[i][k]
+        b += struct.pack("<I", p.bytes)
+    assert ncols * nrows == len(bl)
+    return b
+
+
+def output_files(p: Plan):
+    """Every file the conversion writes, relative to dst, sorted."""
+    names = set()
+    for g in p.appends():
+        for i, k, _, _ in g:
+            for _, _, _, _, dirname in p.blocks(i):
+                vh = dirname.split("/")[1]
+                names.add(f"{p.res_dir(i)}/{dirname}/{vh}_{p.d_name(i, p.d_block_start(i, k))}.tif")
+    names |= {f"{p.res_dir(i)}/mdata.bin" for i in range(p.n_res) if p.selected[i]}
+    return sorted(names)
+
+
+# ------------------------------------------------------------------------------------------------------------------ source
+class Series:
+    """A folder of single-channel 2-D TIFF slices, sorted by name (as the reference's SimpleVolume lists them)."""
+
+    def __init__(self, folder):
+        from . import brickio
+        self.files = brickio.list_tiff_series(folder)
+        if not self.files:
+            raise ValueError(f"no *.tif slices in {folder}")
+        info = brickio.tiff_info(self.files[0])
+        self.fast = bool(info is not None and info[2])
+        if info is not None and info[1] is not None:
+            (ny, nx), dt = info[0], np.dtype(info[1])
+        else:
+            first = np.asarray(brickio._pil().open(self.files[0]))
+            if first.ndim != 2:
+                raise ValueError(f"{self.files[0]}: {first.shape[-1] if first.ndim == 3 else first.ndim}-channel slices: multi-channel "
+                                 "and RGB sources are not supported (one channel of 8 or 16 bits)")
+            (ny, nx), dt = first.shape, first.dtype
+        if dt not in (np.dtype(np.uint8), np.dtype(np.uint16)):
+            raise ValueError(f"{self.files[0]}: {dt} samples; the TeraFly conversion takes 8- or 16-bit single-channel slices")
+        if not self.fast:
+            first = np.asarray(brickio._pil().open(self.files[0]))
+            if first.ndim != 2:
+                raise ValueError(f"{self.files[0]}: multi-channel and RGB sources are not supported (one channel of 8 or 16 bits)")
+        self.shape = (len(self.files), ny, nx)
+        self.dtype = dt
+
+    def read(self, z0, z1, y0, y1, x0, x1, threads=0):
+        from . import brickio
+        files = self.files[z0:z1]
+        if self.fast:
+            try:
+                return brickio.read_tiff_box(files, self.shape[1:], self.dtype, y0, y1, x0, x1, threads=threads)
+            except Exception:
+                pass   # a slice the native reader does not take: Pillow decides
+        Image = brickio._pil()
+        out = np.empty((len(files), y1 - y0, x1 - x0), self.dtype)
+        for k, f in enumerate(files):
+            a = np.asarray(Image.open(f))
+            if a.shape != self.shape[1:] or a.dtype != self.dtype:
+                raise ValueError(f"{f}: {a.dtype} {a.shape} differs from the first slice ({self.dtype} {self.shape[1:]})")
+            out[k] = a[y0:y1, x0:x1]
+        return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ device
+def pyramid_slab(slab, n_levels, halve_d, method, outs):
+    """``mi_pyramid_slab`` on torch tensors: ``slab`` (nz, ny, nx) uint8 / uint16 on the device, ``outs[k]`` the buffer of level
+    k+1 (or None where the level is not needed)."""
+    from . import capi
+    hd = (C.c_int * n_levels)(*[int(v) for v in halve_d])
+    ptrs = (C.c_void_p * n_levels)(*[None if o is None or o.numel() == 0 else o.data_ptr() for o in outs])
+    nz, ny, nx = slab.shape
+    capi.check(capi.lib().mi_pyramid_slab(slab.device.index, capi.current_stream_ptr(slab.device), slab.data_ptr(),
+                                          slab.element_size(), nx, ny, nz, HALVE[method], n_levels, hd, ptrs))
+
+
+def level_shapes(shape, n_levels, halve_d):
+    """(nz, ny, nx) of levels 1..n_levels of a slab of ``shape``."""
+    nz, ny, nx = shape
+    out = []
+    for k in range(n_levels):
+        nz, ny, nx = (nz // 2 if halve_d[k] else nz), ny // 2, nx // 2
+        out.append((nz, ny, nx))
+    return out
+
+
+def _band_rows(p: Plan, nbytes, device, slab_rows=None):
+    """Rows of level 0 per device band: a multiple of 2^(deepest level) whose group band plus its levels fit in half the free
+    device memory (or ``slab_rows``, rounded to that multiple)."""
+    import torch
+    unit = 2 ** (p.n_res - 1)
+    if slab_rows is None:
+        free, _ = torch.cuda.mem_get_info(device)
+        per_row = p.z_max_res * p.width * nbytes * 2      # the band and (at most 1/4 + 1/16 + ...) its levels
+        slab_rows = max(1, int(free // 2 // max(per_row, 1)))
+    return max(unit, (int(slab_rows) // unit) * unit)
+
+
+def convert(src, dst, resolutions="0", halve="mean", block=(-1, -1, -1), isotropic=False, fixed_tiling=False,
+            sub=(-1, -1, -1, -1, -1, -1), compression=True, rows_per_strip=1, bigtiff=False, device=None, slab_rows=None,
+            threads=0, progress=None):
+    """Writes the TeraFly tree of the 2-D series in ``src`` under ``dst`` (an existing folder); ``slab_rows`` fixes the rows of
+    a device band (default: from the free device memory).  Returns the Plan."""
+    import torch
+    from . import capi
+    if halve not in HALVE:
+        raise ValueError(f"--halve={halve}: mean or max")
+    dst = Path(dst)
+    if not dst.is_dir():
+        raise ValueError(f"destination {dst} is not an existing folder (teraconverter -d must exist)")
+    series = Series(src)
+    p = plan(series.shape, resolutions, block, isotropic, fixed_tiling, sub, series.dtype.itemsize)
+    capi.require_gpu()
+    dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+    tdtype = {1: torch.uint8, 2: torch.uint16}[p.bytes]
+    n_lv = p.n_res - 1
+    halve_d = [1 if p.hp[i] == p.hp[i - 1] + 1 else 0 for i in range(1, p.n_res)]
+    band = _band_rows(p, p.bytes, dev, slab_rows)
+    for i in range(p.n_res):
+        if p.selected[i]:
+            for _, _, _, _, dirname in p.blocks(i):
+                (dst / p.res_dir(i) / dirname).mkdir(parents=True, exist_ok=True)
+    pages_in = {}                  # path -> pages written so far
+    appends = p.appends()
+    lib = capi.lib()
+    all_groups = p.groups()
+    for gi, (z, z_size) in enumerate(all_groups):
+        if not appends[gi]:
+            continue
+        host = [None] * p.n_res
+        host[0] = series.read(p.D0 + z, p.D0 + z + z_size, p.V0, p.V0 + p.height, p.H0, p.H0 + p.width, threads)
+        shapes = level_shapes(host[0].shape, n_lv, halve_d)
+        for i in range(1, p.n_res):
+            host[i] = np.empty(shapes[i - 1], host[0].dtype)
+        need = [p.selected[k + 1] or (k % 2 == 1 and k + 1 < n_lv) for k in range(n_lv)]
+        if n_lv > 0:
+            for r0 in range(0, p.height, band):
+                r1 = min(p.height, r0 + band)
+                slab = torch.from_numpy(host[0][:, r0:r1]).to(dev)
+                bshapes = level_shapes(slab.shape, n_lv, halve_d)
+                outs = [torch.empty(s, dtype=tdtype, device=dev) if need[k] else None for k, s in enumerate(bshapes)]
+                pyramid_slab(slab, n_lv, halve_d, halve, outs)
+                for k, o in enumerate(outs):
+                    if o is not None and p.selected[k + 1] and o.numel():
+                        a = r0 >> (k + 1)
+                        host[k + 1][:, a:a + o.shape[1]] = o.cpu().numpy()
+                del slab, outs
+        # pages of this group, appended to their block files in one call
+        paths, first, strides, dims, page0, total = [], [], [], [], [], []
+        for i, k, g0, n in appends[gi]:
+            lv = host[i]
+            for r0, nr, c0, nc, dirname in p.blocks(i):
+                vh = dirname.split("/")[1]
+                path = str(dst / p.res_dir(i) / dirname / f"{vh}_{p.d_name(i, p.d_block_start(i, k))}.tif")
+                view = lv[g0:g0 + n, r0:r0 + nr, c0:c0 + nc]
+                paths.append(os.fsencode(path))
+                first.append(view.ctypes.data)
+                strides += [lv.shape[1] * lv.shape[2], lv.shape[2]]
+                dims += [nc, nr, n]
+                page0.append(pages_in.get(path, 0))
+                total.append(p.deps[i][k])
+                pages_in[path] = pages_in.get(path, 0) + n
+        m = len(paths)
+        capi.check(lib.mi_tiff3d_write_blocks(m, (C.c_char_p * m)(*paths), (C.c_void_p * m)(*first), (C.c_int64 * (2 * m))(*strides),
+                                              (C.c_int * (3 * m))(*dims), (C.c_int * m)(*page0), (C.c_int * m)(*total), p.bytes,
+                                              1 if compression else 0, int(rows_per_strip), 1 if bigtiff else 0, int(threads)))
+        if progress:
+            progress(gi + 1, len(all_groups))
+    write_mdata(p, dst)
+    return p
+
+
+def write_mdata(p: Plan, dst):
+    for i in range(p.n_res):
+        if p.selected[i]:
+            (Path(dst) / p.res_dir(i) / "mdata.bin").write_bytes(mdata_bytes(p, i))
