@@ -20,6 +20,9 @@ ENGINE_AUTO, ENGINE_DIRECT, ENGINE_FFT = 0, 1, 2
 NORTH_SOUTH, WEST_EAST = 0, 1
 SINBLEND, NOBLEND = 0, 1   # mi_blending (include/mi_stitch.h)
 HALVE_MEAN, HALVE_MAX = 0, 1   # mi_halve_method (include/mi_pyramid.h)
+PS_U8, PS_U16, PS_F32 = 0, 1, 2   # mi_pystripe_dtype (include/mi_pystripe.h)
+PS_PADDING = {"reflect": 0, "wrap": 1, "symmetric": 2, "edge": 3}   # mi_pystripe_padding
+PS_DOWN = {"max": 0, "min": 1, "mean": 2}   # mi_pystripe_down
 
 
 MI_ERR_INVALID, MI_ERR_HIP, MI_ERR_FFT, MI_ERR_NOMEM, MI_ERR_UNSUPPORTED = -1, -2, -3, -4, -5  # include/mi_common.h
@@ -51,6 +54,26 @@ class NccParams(C.Structure):
 class NccDescr(C.Structure):
     """mi_ncc_descr == NCC_descr_t (CrossMIPs.h:58-62)."""
     _fields_ = [("coord", C.c_int * 3), ("NCC_maxs", C.c_float * 3), ("NCC_widths", C.c_int * 3)]
+
+
+class PystripeParams(C.Structure):
+    """mi_pystripe_params (include/mi_pystripe.h)."""
+    _fields_ = [("sigma1", C.c_double), ("sigma2", C.c_double), ("level", C.c_int), ("padding_mode", C.c_int),
+                ("bidirectional", C.c_int), ("down_y", C.c_int), ("down_x", C.c_int), ("down_method", C.c_int),
+                ("use_flat", C.c_int), ("dark", C.c_float), ("convert_to_16bit", C.c_int), ("convert_to_8bit", C.c_int),
+                ("bit_shift", C.c_int), ("out_dtype", C.c_int), ("flip_upside_down", C.c_int), ("rotate", C.c_int),
+                ("log_output", C.c_int), ("max_batch", C.c_int), ("keep_uniform", C.c_int)]
+
+
+PS_MAX_LEVELS = 24  # MI_PS_MAX_LEVELS
+
+
+class PystripeInfo(C.Structure):
+    """mi_pystripe_info (include/mi_pystripe.h)."""
+    _fields_ = [("ny", C.c_int), ("nx", C.c_int), ("base_pad", C.c_int), ("pad_y", C.c_int), ("pad_x", C.c_int),
+                ("padded_ny", C.c_int), ("padded_nx", C.c_int), ("levels", C.c_int), ("coef_ny", C.c_int * PS_MAX_LEVELS),
+                ("coef_nx", C.c_int * PS_MAX_LEVELS), ("out_ny", C.c_int), ("out_nx", C.c_int), ("out_dtype", C.c_int),
+                ("integer_kind", C.c_int), ("max_batch", C.c_int), ("scratch_bytes_per_tile", C.c_size_t)]
 
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
@@ -142,6 +165,13 @@ SIGNATURES = {
     "mi_tiff3d_write_blocks": (_i, [_i, C.POINTER(C.c_char_p), C.POINTER(_vp), C.POINTER(C.c_int64), _ip, _ip, _ip, _i, _i, _i, _i,
                                     _i]),
     "mi_tiff_lzw_encode": (_i, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    # mi_pystripe.h
+    "mi_pystripe_plan_create": (_i, [_i, _i, _i, _i, C.POINTER(PystripeParams), C.POINTER(_vp)]),
+    "mi_pystripe_plan_destroy": (_i, [_vp]),
+    "mi_pystripe_plan_info": (_i, [_vp, C.POINTER(PystripeInfo)]),
+    "mi_pystripe_derive": (_i, [_i, _i, _i, C.POINTER(PystripeParams), C.POINTER(PystripeInfo)]),
+    "mi_pystripe_run": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64]),
+    "mi_pystripe_pad_size": (_i, [_i, _i, C.c_double]),
     # mi_crossmips.h
     "mi_ncc_default_params": (None, [_i, _i, _i, C.POINTER(NccParams)]),
     "mi_ncc_mips": (_i, [_i, _vp, _vp, _vp] + [_i] * 10 + [C.POINTER(NccParams), C.POINTER(NccDescr)]),

@@ -1,0 +1,800 @@
+// pystripe tile preprocessing (pystripe/core.py process_img :1190, filter_streaks :982, filter_subband :927-940,
+// np_filter_coefficient :749) on batches of equally shaped 2-D tiles.  Every launch covers the whole batch (grid z / y = tile):
+// one 2048^2 tile leaves most of the device idle at the deep wavelet levels.
+//
+//   load      the first analysis level reads the tile itself: integer load, log1p and the numpy.pad index map (reflect / wrap /
+//             symmetric / edge) are folded into its addressing, so the padded image is never written.  The row pass runs over
+//             the SOURCE rows only; the column pass looks rows up through the same map.
+//   analysis  out[i] = sum_t F[t] in[sym(2 i + 1 - t)], floor((n + 17) / 2) coefficients ('symmetric', db9); rows then columns:
+//             L, H along axis -1, then A, cH (from L) and cV, cD (from H) along axis -2 -- cH is the high-pass along axis -2 of
+//             the low-pass along axis -1, PyWavelets' 'da'.
+//   notch     np_filter_coefficient multiplies scipy.fftpack.rfft's packed spectrum [r0, r1, i1, r2, i2, ...] by
+//             g[j] = 1 - exp(-j^2 / (2 s^2)) BY PACKED POSITION (real part of bin k: g[2k-1], imaginary part: g[2k]), so it is
+//             not a convolution.  1 - g[j] is exactly 0 in float32 beyond j ~ 5.9 s: evaluated as c - irfft((1 - g) * rfft(c))
+//             over those low positions only, as direct sums in float64 folded over the j <-> n - j symmetry of the twiddles (up to
+//             four lines, the twiddle table and their kept spectrum stay in LDS).
+//   synthesis out[j] = sum_k a[k] Lo_R[j + 16 - 2 k] + d[k] Hi_R[j + 16 - 2 k]; a thread makes the pair (2p, 2p + 1), which shares
+//             its nine k.  waverec2's trim of the approximation is a smaller extent read with the wider stride.
+//   store     the last synthesis level computes only the un-padded window and finishes every sample in registers: expm1, rint + clip
+//             (integer tiles), dark, 8 / 16-bit conversion, flip and rotation in the store address.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "mi_internal.h"
+#include "mi_pystripe.h"
+
+namespace mi {
+namespace {
+
+constexpr int LF = 18;           // db9
+constexpr int kRowBlock = 256;   // outputs of one block of the analysis row pass
+constexpr int kMinLength = 34;   // filter_streaks :1092
+using i64 = long long;
+
+// Lo_R of db9 (the table of destripe.hip; tests recompute it by spectral factorisation)
+const double kLoR[LF] = {3.80779473638783381e-02,  2.43834674612590230e-01,  6.04823123690111153e-01,  6.57288078051299962e-01,
+                         1.33197385825007591e-01,  -2.93273783279174305e-01, -9.68407832229760124e-02, 1.48540749338105876e-01,
+                         3.07256814793338794e-02,  -6.76328290613307237e-02, 2.50947114831909018e-04,  2.23616621236789742e-02,
+                         -4.72320475775138936e-03, -4.28150368246343286e-03, 1.84764688305622871e-03,  2.30385763523196190e-04,
+                         -2.51963188942710503e-04, 3.93473203162716365e-05};
+
+struct Filters {
+    float lo_d[LF], hi_d[LF], lo_r[LF], hi_r[LF];
+};
+
+Filters make_filters() {
+    Filters f;
+    for (int t = 0; t < LF; ++t) {
+        f.lo_r[t] = (float)kLoR[t];
+        f.hi_r[t] = (float)(kLoR[LF - 1 - t] * ((t & 1) ? -1.0 : 1.0));   // qmf
+    }
+    for (int t = 0; t < LF; ++t) {
+        f.lo_d[t] = f.lo_r[LF - 1 - t];
+        f.hi_d[t] = f.hi_r[LF - 1 - t];
+    }
+    return f;
+}
+
+enum { MAP_IDENTITY = 4 };
+enum { OUT_FLOAT = 0, OUT_TO8 = 1, OUT_CLIPCAST = 2 };
+
+__device__ __forceinline__ int sym_index(int j, int n) {   // half-point symmetric extension, any distance
+    const int p = 2 * n;
+    j %= p;
+    if (j < 0) j += p;
+    return j < n ? j : p - 1 - j;
+}
+
+// numpy.pad's index map: padded coordinate i (pad samples in front) -> source index in [0, n)
+__device__ __forceinline__ int pad_index(int i, int pad, int n, int mode) {
+    int q = i - pad;
+    if (mode == MAP_IDENTITY || (q >= 0 && q < n)) return q;
+    if (mode == MI_PS_EDGE) return q < 0 ? 0 : n - 1;
+    if (mode == MI_PS_WRAP) {
+        q %= n;
+        return q < 0 ? q + n : q;
+    }
+    if (mode == MI_PS_SYMMETRIC) return sym_index(q, n);
+    if (n == 1) return 0;   // reflect
+    const int p = 2 * n - 2;
+    q %= p;
+    if (q < 0) q += p;
+    return q < n ? q : p - q;
+}
+
+// where a level's input comes from: the tile itself (any dtype, through the padding map, log1p) or a float image of the pyramid
+struct Src {
+    const void* p;
+    i64 tile_stride;   // samples
+    int dtype, ny, nx, row_stride;
+    int pad, mode, logp;
+};
+
+__device__ __forceinline__ float src_load(const Src& s, i64 tile, int y, int x) {
+    const i64 o = tile * s.tile_stride + (i64)y * s.row_stride + x;
+    float v;
+    if (s.dtype == MI_PS_U16) v = (float)static_cast<const uint16_t*>(s.p)[o];
+    else if (s.dtype == MI_PS_U8) v = (float)static_cast<const uint8_t*>(s.p)[o];
+    else v = static_cast<const float*>(s.p)[o];
+    return s.logp ? log1pf(v) : v;
+}
+
+// what happens to a sample after the filter (process_img :1322-1379 and the tail of filter_streaks :1150-1158)
+struct Sink {
+    void* out;
+    i64 tile_stride;        // samples
+    int ny, nx;             // the un-padded tile
+    int pad;                // rows / columns in front of it in the padded image
+    int filtered;           // the value is in the log domain: expm1 (and rint + clip for integer tiles)
+    int log_out;
+    int integer_kind;
+    float in_max;
+    float dark;
+    int mode, shift, out_dtype;
+    float cast_max;
+    int flip, rot;
+    const int* varies;      // per tile: 0 = uniform tile -> zeros
+};
+
+__device__ __forceinline__ void sink_store(const Sink& k, i64 tile, int y, int x, float v) {
+    if (k.log_out) {
+        static_cast<float*>(k.out)[tile * k.tile_stride + (i64)y * k.nx + x] = v;
+        return;
+    }
+    if (k.filtered) {
+        v = expm1f(v);
+        if (k.integer_kind) v = fminf(fmaxf(rintf(v), 0.f), k.in_max);
+    }
+    if (k.dark > 0.f) {
+        v = v > k.dark ? v - k.dark : 0.f;
+        if (k.integer_kind) v = truncf(v);
+    }
+    if (!k.varies[tile]) v = 0.f;
+    if (k.flip) y = k.ny - 1 - y;
+    int oy = y, ox = x, onx = k.nx;
+    if (k.rot == 1) { oy = k.nx - 1 - x; ox = y; onx = k.ny; }
+    else if (k.rot == 2) { oy = k.ny - 1 - y; ox = k.nx - 1 - x; }
+    else if (k.rot == 3) { oy = x; ox = k.ny - 1 - y; onx = k.ny; }
+    const i64 o = tile * k.tile_stride + (i64)oy * onx + ox;
+    if (k.mode == OUT_FLOAT) {
+        static_cast<float*>(k.out)[o] = v;
+        return;
+    }
+    int u;
+    if (k.mode == OUT_TO8) {
+        u = (int)fminf(fmaxf(v, 0.f), 65535.f);
+        u = (u > 0 && u < (1 << k.shift)) ? 1 : (u >> k.shift);
+        u = min(u, 255);
+    } else {
+        u = (int)fminf(fmaxf(v, 0.f), k.cast_max);
+    }
+    if (k.out_dtype == MI_PS_U16) static_cast<uint16_t*>(k.out)[o] = (uint16_t)u;
+    else static_cast<uint8_t*>(k.out)[o] = (uint8_t)u;
+}
+
+// is_uniform_2d (:107): varies[tile] |= any sample differs from the first.  VEC: 16-byte loads (the tile's bytes are a multiple of 16 and
+// the batch is 16-byte aligned).
+template <class T, bool VEC>
+__global__ void __launch_bounds__(256) uniform_kernel(const T* in, i64 npix, int* varies) {
+    const i64 tile = blockIdx.y;
+    const T* p = in + tile * npix;
+    const T first = p[0];
+    bool d = false;
+    const i64 t0 = (i64)blockIdx.x * blockDim.x + threadIdx.x, step = (i64)gridDim.x * blockDim.x;
+    if (VEC) {
+        constexpr int E = 16 / sizeof(T);
+        const uint4* p4 = reinterpret_cast<const uint4*>(p);
+        for (i64 i = t0; i < npix / E; i += step) {
+            union { uint4 v; T e[E]; } u;
+            u.v = p4[i];
+#pragma unroll
+            for (int q = 0; q < E; ++q) d |= (u.e[q] != first);
+        }
+    } else {
+        for (i64 i = t0; i < npix; i += step) d |= (p[i] != first);
+    }
+    // one atomic per wave that saw a difference, and none once the flag is up (a stale read only costs a redundant atomic)
+    if (__any(d) && (threadIdx.x & 63) == 0 && __atomic_load_n(&varies[tile], __ATOMIC_RELAXED) == 0) atomicOr(&varies[tile], 1);
+}
+
+template <class T>
+int launch_uniform(hipStream_t st, const void* in, i64 npix, int cnt, int* varies) {
+    const bool vec = (npix * sizeof(T)) % 16 == 0 && reinterpret_cast<uintptr_t>(in) % 16 == 0;
+    const i64 items = vec ? npix * (i64)sizeof(T) / 16 : npix;
+    const dim3 grid((unsigned)std::max<i64>(1, std::min<i64>((items + 256 * 4 - 1) / (256 * 4), 2048)), cnt);
+    if (vec) hipLaunchKernelGGL((uniform_kernel<T, true>), grid, dim3(256), 0, st, static_cast<const T*>(in), npix, varies);
+    else hipLaunchKernelGGL((uniform_kernel<T, false>), grid, dim3(256), 0, st, static_cast<const T*>(in), npix, varies);
+    return launch_check("uniform_kernel");
+}
+
+// flat field and skimage's block_reduce (zero padding up to a multiple of the block) -> a float32 tile
+__global__ void __launch_bounds__(256) pre_kernel(Src s, const float* flat, int by, int bx, int method, float* stage, int ny, int nx) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const i64 tile = blockIdx.z;
+    if (x >= nx || y >= ny) return;
+    double sum = 0.0;
+    float mx = -INFINITY, mn = INFINITY;
+    for (int dy = 0; dy < by; ++dy)
+        for (int dx = 0; dx < bx; ++dx) {
+            const int yy = y * by + dy, xx = x * bx + dx;
+            float v = 0.f;
+            if (yy < s.ny && xx < s.nx) {
+                v = src_load(s, tile, yy, xx);
+                if (flat) v = v / flat[(i64)yy * s.nx + xx];
+            }
+            sum += (double)v;
+            mx = fmaxf(mx, v);
+            mn = fminf(mn, v);
+        }
+    const float r = method == MI_PS_DOWN_MAX ? mx : method == MI_PS_DOWN_MIN ? mn : (float)(sum / (double)(by * bx));
+    stage[tile * ((i64)ny * nx) + (i64)y * nx + x] = r;
+}
+
+// no stripe filter: every sample straight to the sink
+__global__ void __launch_bounds__(256) point_kernel(Src s, Sink k) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= k.nx || y >= k.ny) return;
+    sink_store(k, blockIdx.z, y, x, src_load(s, blockIdx.z, y, x));
+}
+
+// analysis along axis -1.  n: extent of the (padded) row, m = (n + 17) / 2 outputs.  A block stages the 2 * 256 + 16 inputs of its
+// 256 outputs in LDS (the index maps and log1p are applied once per staged sample), then every thread runs its 18 taps on them.
+__global__ void __launch_bounds__(kRowBlock) ana_rows_kernel(Src s, int n, int m, float* L, float* H, i64 out_tile_stride, Filters f) {
+    __shared__ float sh[2 * kRowBlock + 16];
+    const int i0 = blockIdx.x * kRowBlock, row = blockIdx.y;
+    const i64 tile = blockIdx.z;
+    const int base = 2 * i0 - 16;
+    for (int q = threadIdx.x; q < 2 * kRowBlock + 16; q += kRowBlock) {
+        const int j = sym_index(base + q, n);
+        sh[q] = src_load(s, tile, row, pad_index(j, s.pad, s.nx, s.mode));
+    }
+    __syncthreads();
+    const int i = i0 + threadIdx.x;
+    if (i >= m) return;
+    float lo = 0.f, hi = 0.f;
+#pragma unroll
+    for (int t = 0; t < LF; ++t) {
+        const float v = sh[2 * threadIdx.x + 17 - t];
+        lo = fmaf(f.lo_d[t], v, lo);
+        hi = fmaf(f.hi_d[t], v, hi);
+    }
+    const i64 o = tile * out_tile_stride + (i64)row * m + i;
+    L[o] = lo;
+    H[o] = hi;
+}
+
+// analysis along axis -2 of L and H ([rows][w], rows looked up through the padding map at the first level): A, cH from L and cV, cD
+// from H, each [m][w].  Threads run along x, so every load is a contiguous row segment.
+__global__ void __launch_bounds__(256) ana_cols_kernel(const float* L, const float* H, i64 in_tile_stride, int n, int m, int w, int pad,
+                                                       int src_rows, int mode, float* A, i64 a_tile_stride, float* cH, float* cV,
+                                                       float* cD, i64 d_tile_stride, Filters f) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), i = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const i64 tile = blockIdx.z;
+    if (x >= w || i >= m) return;
+    const float* l = L + tile * in_tile_stride + x;
+    const float* h = H + tile * in_tile_stride + x;
+    float a = 0.f, ch = 0.f, cv = 0.f, cd = 0.f;
+#pragma unroll
+    for (int t = 0; t < LF; ++t) {
+        const int r = pad_index(sym_index(2 * i + 1 - t, n), pad, src_rows, mode);
+        const float lv = l[(i64)r * w], hv = h[(i64)r * w];
+        a = fmaf(f.lo_d[t], lv, a);
+        ch = fmaf(f.hi_d[t], lv, ch);
+        cv = fmaf(f.lo_d[t], hv, cv);
+        cd = fmaf(f.hi_d[t], hv, cd);
+    }
+    const i64 o = (i64)i * w + x;
+    A[tile * a_tile_stride + o] = a;
+    cH[tile * d_tile_stride + o] = ch;
+    cV[tile * d_tile_stride + o] = cv;
+    cD[tile * d_tile_stride + o] = cd;
+}
+
+// The packed-position notch on lines of n samples (element stride es, line stride ls, in place).  LDS: the twiddle table
+// (cos, sin)(2 pi j / n), R lines, their kept spectrum.  Phase 1: thread = bin k, the R lines share every twiddle read.  Phase 2:
+// thread = sample pair (j, n - j) -- the sums are folded over that symmetry.  kp packed positions have a non-zero weight 1 - g; bins 0 .. kb-1 cover them.
+template <int R>
+__global__ void __launch_bounds__(512) notch_kernel(float* c, i64 tile_stride, int n, int nlines, i64 es, i64 ls, const double2* tw_g,
+                                                    const float* wt, int kp, int kb) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double2* tw = reinterpret_cast<double2*>(smem);
+    double2* S = tw + n;
+    float* xs = reinterpret_cast<float*>(S + (size_t)R * kb);
+    const int line0 = blockIdx.x * R;
+    float* base = c + (i64)blockIdx.y * tile_stride;
+    for (int j = threadIdx.x; j < n; j += blockDim.x) tw[j] = tw_g[j];
+    for (int e = threadIdx.x; e < R * n; e += blockDim.x) {
+        int r, j;
+        if (es == 1) { r = e / n; j = e - r * n; }
+        else { j = e / R; r = e - j * R; }
+        xs[r * n + j] = (line0 + r < nlines) ? base[(i64)(line0 + r) * ls + (i64)j * es] : 0.f;
+    }
+    __syncthreads();
+    // fold: cos is even and sin odd under j -> n - j, so the samples j and n - j share a twiddle: e_j = x_j + x_{n-j} meets the cosine
+    // only, o_j = x_j - x_{n-j} the sine only (kept in place of x_j and x_{n-j}); j = 0 and, for an even n, j = n / 2 stand alone.
+    // Half the float64 sums of the plain form, in both phases.
+    const int hp = (n - 1) / 2;   // pairs j = 1 .. hp
+    for (int e = threadIdx.x; e < R * hp; e += blockDim.x) {
+        const int r = e / hp, j = 1 + e - r * hp;
+        const float a = xs[r * n + j], b = xs[r * n + n - j];
+        xs[r * n + j] = a + b;
+        xs[r * n + n - j] = a - b;
+    }
+    __syncthreads();
+    const double inv_n = 1.0 / (double)n;
+    const bool even = (n & 1) == 0;
+    for (int k = threadIdx.x; k < kb; k += blockDim.x) {
+        double re[R], im[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            re[r] = (double)xs[r * n];
+            if (even) re[r] += (k & 1) ? -(double)xs[r * n + n / 2] : (double)xs[r * n + n / 2];
+            im[r] = 0.0;
+        }
+        int idx = k;
+        for (int j = 1; j <= hp; ++j) {
+            const double2 t = tw[idx];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                re[r] = fma((double)xs[r * n + j], t.x, re[r]);
+                im[r] = fma(-(double)xs[r * n + n - j], t.y, im[r]);
+            }
+            idx += k;
+            if (idx >= n) idx -= n;
+        }
+        // gains by packed position: real part of bin k at 2k - 1, imaginary part at 2k; DC at 0; the Nyquist bin of an even n has no
+        // imaginary part and counts once
+        const int pr = k == 0 ? 0 : 2 * k - 1, pi = 2 * k;
+        const double wr = pr < kp ? (double)wt[pr] : 0.0;
+        const double wi = (k == 0 || pi >= kp || pi >= n) ? 0.0 : (double)wt[pi];
+        const double sc = (k == 0 || 2 * k == n) ? inv_n : 2.0 * inv_n;
+#pragma unroll
+        for (int r = 0; r < R; ++r) S[r * kb + k] = make_double2(re[r] * wr * sc, im[r] * wi * sc);
+    }
+    __syncthreads();
+    // thread = the pair (j, n - j): smooth_j = S_0 + A - B, smooth_{n-j} = S_0 + A + B with A the cosine and B the sine sum
+    for (int j = threadIdx.x; j <= n / 2; j += blockDim.x) {
+        double A[R], B[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) A[r] = B[r] = 0.0;
+        int idx = j;
+        for (int k = 1; k < kb; ++k) {
+            const double2 t = tw[idx];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double2 sv = S[r * kb + k];
+                A[r] = fma(sv.x, t.x, A[r]);
+                B[r] = fma(sv.y, t.y, B[r]);
+            }
+            idx += j;
+            if (idx >= n) idx -= n;
+        }
+        const bool twin = j != 0 && 2 * j != n;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (line0 + r >= nlines) continue;
+            float* line = base + (i64)(line0 + r) * ls;
+            const double s0 = S[r * kb].x;
+            line[(i64)j * es] = line[(i64)j * es] - (float)(s0 + A[r] - B[r]);
+            if (twin) line[(i64)(n - j) * es] = line[(i64)(n - j) * es] - (float)(s0 + A[r] + B[r]);
+        }
+    }
+}
+
+// synthesis along axis -2: rows 2p, 2p + 1 of lo1 (from a, cH) and hi1 (from cV, cD); blockIdx.z = 2 * tile + which.  a has its
+// own row stride (the approximation of a deeper level is one row / column larger than the details: waverec2 trims it).
+__global__ void __launch_bounds__(256) syn_cols_kernel(const float* a, i64 a_tile_stride, int a_stride, const float* cH, const float* cV,
+                                                       const float* cD, i64 d_tile_stride, int w, int p0, int p1, int s0, float* lo1,
+                                                       float* hi1, i64 out_tile_stride, Filters f) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), p = p0 + blockIdx.y * 4 + (threadIdx.x >> 6);
+    const i64 tile = blockIdx.z >> 1;
+    const int which = blockIdx.z & 1;
+    if (x >= w || p >= p1) return;
+    const float* lo = which ? cV + tile * d_tile_stride : a + tile * a_tile_stride;
+    const float* hi = (which ? cD : cH) + tile * d_tile_stride;
+    const int lo_stride = which ? w : a_stride;
+    float e = 0.f, o = 0.f;
+#pragma unroll
+    for (int d = 0; d < 9; ++d) {
+        const float av = lo[(i64)(p + d) * lo_stride + x], dv = hi[(i64)(p + d) * w + x];
+        e = fmaf(av, f.lo_r[16 - 2 * d], e);
+        e = fmaf(dv, f.hi_r[16 - 2 * d], e);
+        o = fmaf(av, f.lo_r[17 - 2 * d], o);
+        o = fmaf(dv, f.hi_r[17 - 2 * d], o);
+    }
+    float* dst = (which ? hi1 : lo1) + tile * out_tile_stride;
+    dst[(i64)(2 * p) * w + x] = e;
+    if (2 * p + 1 < s0) dst[(i64)(2 * p + 1) * w + x] = o;
+}
+
+// synthesis along axis -1: columns 2p, 2p + 1 of rows y0 + blockIdx.y.  FINAL: only the un-padded window, through the sink.
+template <bool FINAL>
+__global__ void __launch_bounds__(256) syn_rows_kernel(const float* lo1, const float* hi1, i64 in_tile_stride, int w, int y0, int p0, int p1,
+                                                       int s1, float* out, i64 out_tile_stride, Sink k, Filters f) {
+    const int p = p0 + blockIdx.x * 256 + threadIdx.x, y = y0 + blockIdx.y;
+    const i64 tile = blockIdx.z;
+    if (p >= p1) return;
+    const float* lo = lo1 + tile * in_tile_stride + (i64)y * w + p;
+    const float* hi = hi1 + tile * in_tile_stride + (i64)y * w + p;
+    float e = 0.f, o = 0.f;
+#pragma unroll
+    for (int d = 0; d < 9; ++d) {
+        const float av = lo[d], dv = hi[d];
+        e = fmaf(av, f.lo_r[16 - 2 * d], e);
+        e = fmaf(dv, f.hi_r[16 - 2 * d], e);
+        o = fmaf(av, f.lo_r[17 - 2 * d], o);
+        o = fmaf(dv, f.hi_r[17 - 2 * d], o);
+    }
+    if (FINAL) {
+        const int yy = y - k.pad, x0 = 2 * p - k.pad;
+        if (x0 >= 0 && x0 < k.nx) sink_store(k, tile, yy, x0, e);
+        if (x0 + 1 >= 0 && x0 + 1 < k.nx) sink_store(k, tile, yy, x0 + 1, o);
+    } else {
+        float* dst = out + tile * out_tile_stride + (i64)y * s1;
+        dst[2 * p] = e;
+        if (2 * p + 1 < s1) dst[2 * p + 1] = o;
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------
+
+int notch_rise_point(double sigma, double rise) {   // :670
+    return (int)(std::sqrt(-2.0 * sigma * sigma * std::log(1.0 - rise)) + 0.5) / 2 * 2;
+}
+
+int pad_size(int ny, int nx, double sigma) {   // calculate_pad_size :681
+    if (sigma == 0) return 0;
+    const double x = nx + 1.0, y = ny + 1.0, c = 5e14;
+    const double s = std::sqrt(x * x - 2 * x * y + y * y + 4 * c);
+    const double r = std::nearbyint((1.0 - std::exp((x + y - s) / (4 * sigma * sigma))) * 100.0) / 100.0 - 0.01;
+    return notch_rise_point(sigma, std::min(r, 0.5));
+}
+
+int max_level(int n) { return n >= LF - 1 ? std::max((int)std::floor(std::log2((double)n / (LF - 1))), 0) : 0; }   // pywt.dwt_max_level
+
+size_t round16(size_t v) { return (v + 15) / 16 * 16; }
+
+struct NotchTab {          // one (pass, level, axis)
+    int n, kp, kb, R, threads;
+    size_t lds;
+    size_t tw_off, w_off;  // into the plan's table buffers (elements)
+};
+
+struct Plan {
+    int dev = 0, in_ny = 0, in_nx = 0, in_dtype = 0;
+    mi_pystripe_params prm{};
+    mi_pystripe_info info{};
+    bool filter = false, pre = false;
+    int passes = 0;
+    Filters f{};
+    int h[MI_PS_MAX_LEVELS + 1] = {0}, w[MI_PS_MAX_LEVELS + 1] = {0};   // extents per level, [0] = padded image
+    // per-tile scratch, offsets in floats
+    size_t off_stage = 0, off_P = 0, off_rowL = 0, off_rowH = 0, off_A[MI_PS_MAX_LEVELS + 1] = {0}, off_cH[MI_PS_MAX_LEVELS + 1] = {0},
+           off_cV[MI_PS_MAX_LEVELS + 1] = {0}, off_cD[MI_PS_MAX_LEVELS + 1] = {0};
+    size_t sz_stage = 0, sz_P = 0, sz_row = 0, sz_A[MI_PS_MAX_LEVELS + 1] = {0}, sz_d[MI_PS_MAX_LEVELS + 1] = {0};
+    std::vector<NotchTab> tabs;   // [pass][level 1..L][axis 0: cH along -1, 1: cV along -2]
+    DevBuf tw_buf, w_buf, scratch, varies;
+    i64 cap = 0;
+};
+
+// sizes, modes and the scratch layout: everything that needs no device
+int derive(int ny_in, int nx_in, int in_dtype, const mi_pystripe_params& q, Plan& P) {
+    MI_REQUIRE(ny_in > 0 && nx_in > 0, "mi_pystripe: tile of %d x %d", ny_in, nx_in);
+    MI_REQUIRE(in_dtype >= MI_PS_U8 && in_dtype <= MI_PS_F32, "mi_pystripe: in_dtype %d (0 uint8, 1 uint16, 2 float32)", in_dtype);
+    MI_REQUIRE(q.out_dtype >= MI_PS_U8 && q.out_dtype <= MI_PS_F32, "mi_pystripe: out_dtype %d (0 uint8, 1 uint16, 2 float32)", q.out_dtype);
+    MI_REQUIRE(q.sigma1 >= 0 && q.sigma2 >= 0, "mi_pystripe: sigma (%g, %g) is negative", q.sigma1, q.sigma2);
+    P.filter = q.sigma1 > 0 || q.sigma2 > 0;
+    MI_REQUIRE(!P.filter || (q.sigma1 > 0 && q.sigma2 > 0), "np_notch: sigma must be positive (sigma = (%g, %g))", q.sigma1, q.sigma2);
+    MI_REQUIRE(q.padding_mode >= MI_PS_REFLECT && q.padding_mode <= MI_PS_EDGE, "mi_pystripe: padding_mode %d", q.padding_mode);
+    MI_REQUIRE(q.down_method >= MI_PS_DOWN_MAX && q.down_method <= MI_PS_DOWN_MEAN, "mi_pystripe: down_method %d", q.down_method);
+    MI_REQUIRE(q.down_y >= 0 && q.down_x >= 0 && (q.down_y > 0) == (q.down_x > 0), "mi_pystripe: down_sample (%d, %d)", q.down_y, q.down_x);
+    MI_REQUIRE(q.rotate == 0 || q.rotate == 90 || q.rotate == 180 || q.rotate == 270, "mi_pystripe: rotate %d (0, 90, 180, 270)", q.rotate);
+    MI_REQUIRE(q.level >= 0 && q.level <= MI_PS_MAX_LEVELS, "mi_pystripe: level %d", q.level);
+    MI_REQUIRE(!(q.convert_to_16bit && q.convert_to_8bit), "mi_pystripe: convert_to_16bit and convert_to_8bit are both set");
+    MI_REQUIRE(!q.convert_to_8bit || (q.bit_shift >= 0 && q.bit_shift <= 8), "right shift should be between 0 and 8 (bit_shift_to_right = %d)",
+               q.bit_shift);
+    P.in_ny = ny_in; P.in_nx = nx_in; P.in_dtype = in_dtype; P.prm = q;
+    mi_pystripe_info& I = P.info;
+    std::memset(&I, 0, sizeof I);
+    const bool down = q.down_y > 0;
+    P.pre = down || q.use_flat;
+    I.ny = down ? (ny_in + q.down_y - 1) / q.down_y : ny_in;
+    I.nx = down ? (nx_in + q.down_x - 1) / q.down_x : nx_in;
+    I.integer_kind = in_dtype != MI_PS_F32 && !q.use_flat && !(down && q.down_method == MI_PS_DOWN_MEAN);
+    I.max_batch = q.max_batch > 0 ? q.max_batch : 16;
+    // grid limits: rows go to gridDim.y, tiles (twice, in the column synthesis) to gridDim.z
+    MI_REQUIRE(I.max_batch <= 16384, "mi_pystripe: max_batch %d (at most 16384 tiles per launch)", I.max_batch);
+    if (q.log_output) {
+        MI_REQUIRE(P.filter, "mi_pystripe: log_output needs a stripe filter (sigma > 0)");
+        I.out_ny = I.ny; I.out_nx = I.nx; I.out_dtype = MI_PS_F32;
+    } else {
+        const bool swap = q.rotate == 90 || q.rotate == 270;
+        I.out_ny = swap ? I.nx : I.ny;
+        I.out_nx = swap ? I.ny : I.nx;
+        I.out_dtype = q.out_dtype;
+    }
+    P.passes = !P.filter ? 0 : (q.sigma1 == q.sigma2 ? 1 : 2);
+    size_t off = 0;
+    auto take = [&off](size_t n) { const size_t o = off; off += (n + 3) / 4 * 4; return o; };
+    if (P.pre) { P.sz_stage = (size_t)I.ny * I.nx; P.off_stage = take(P.sz_stage); }
+    if (P.filter) {
+        I.base_pad = pad_size(I.ny, I.nx, std::max(q.sigma1, q.sigma2));
+        I.pad_y = I.ny % 2; I.pad_x = I.nx % 2;
+        if (I.ny + 2 * I.base_pad + I.pad_y < kMinLength) I.pad_y = kMinLength - (I.ny + 2 * I.base_pad);
+        if (I.nx + 2 * I.base_pad + I.pad_x < kMinLength) I.pad_x = kMinLength - (I.nx + 2 * I.base_pad);
+        I.padded_ny = I.ny + 2 * I.base_pad + I.pad_y;
+        I.padded_nx = I.nx + 2 * I.base_pad + I.pad_x;
+        MI_REQUIRE((i64)I.padded_ny * I.padded_nx < (1ll << 31), "mi_pystripe: padded tile of %d x %d samples", I.padded_ny, I.padded_nx);
+        MI_REQUIRE(I.padded_ny <= 65535, "mi_pystripe: padded tile of %d rows (at most 65535)", I.padded_ny);
+        I.levels = q.level > 0 ? q.level : std::min(max_level(I.padded_ny), max_level(I.padded_nx));
+        MI_REQUIRE(I.levels >= 1, "mi_pystripe: no wavelet level for a padded tile of %d x %d", I.padded_ny, I.padded_nx);
+        P.h[0] = I.padded_ny; P.w[0] = I.padded_nx;
+        for (int l = 1; l <= I.levels; ++l) {
+            P.h[l] = (P.h[l - 1] + LF - 1) / 2;
+            P.w[l] = (P.w[l - 1] + LF - 1) / 2;
+            I.coef_ny[l - 1] = P.h[l]; I.coef_nx[l - 1] = P.w[l];
+            // a synthesis pair reads rows p .. p + 8 of a level: s = 2 m - 16 outputs need m >= 9, true for every m >= (0 + 17) / 2 + 1
+            MI_REQUIRE(P.h[l] >= 9 && P.w[l] >= 9, "mi_pystripe: level %d has %d x %d coefficients", l, P.h[l], P.w[l]);
+        }
+        if (P.passes == 2) { P.sz_P = (size_t)P.h[0] * P.w[0]; P.off_P = take(P.sz_P); }
+        P.sz_row = (size_t)(P.h[0] + 1) * P.w[1];   // L / H of the first level; lo1 / hi1 of the synthesis (one more row when odd)
+        P.off_rowL = take(P.sz_row);
+        P.off_rowH = take(P.sz_row);
+        for (int l = 1; l <= I.levels; ++l) {
+            P.sz_A[l] = (size_t)(P.h[l] + 1) * (P.w[l] + 1);   // also holds the level's reconstruction (2 m' - 16 <= m + 1)
+            P.sz_d[l] = (size_t)P.h[l] * P.w[l];
+            P.off_A[l] = take(P.sz_A[l]);
+            P.off_cH[l] = take(P.sz_d[l]);
+            P.off_cV[l] = take(P.sz_d[l]);
+            P.off_cD[l] = take(P.sz_d[l]);
+        }
+    }
+    I.scratch_bytes_per_tile = off * sizeof(float);
+    // the output conversion (:1361-1369)
+    const int cur = I.integer_kind ? in_dtype : MI_PS_F32;
+    if (!q.log_output) {
+        if (q.convert_to_16bit && cur != MI_PS_U16)
+            MI_REQUIRE(q.out_dtype == MI_PS_U16, "mi_pystripe: convert_to_16bit with out_dtype %d", q.out_dtype);
+        else if (q.convert_to_8bit && cur != MI_PS_U8)
+            MI_REQUIRE(q.out_dtype == MI_PS_U8, "mi_pystripe: convert_to_8bit with out_dtype %d", q.out_dtype);
+    }
+    return MI_OK;
+}
+
+int build_tables(Plan& P) {
+    const mi_pystripe_info& I = P.info;
+    std::vector<double2> tw;
+    std::vector<float> wt;
+    P.tabs.clear();
+    for (int pass = 0; pass < P.passes; ++pass) {
+        const double sigma = pass == 0 ? P.prm.sigma1 : P.prm.sigma2;
+        for (int l = 1; l <= I.levels; ++l)
+            for (int axis = 0; axis < 2; ++axis) {
+                NotchTab t{};
+                t.n = axis == 0 ? P.w[l] : P.h[l];
+                // np_filter_coefficient :750: sigma' = coef.shape[axis + 1] * sigma / padded extent of the OTHER axis' count
+                const double sp = axis == 0 ? P.h[l] * (sigma / I.padded_ny) : P.w[l] * (sigma / I.padded_nx);
+                const float den = 2.0f * (float)(sp * sp);   // float32(2) * sigma ** 2 lands in float32 (np_notch :660)
+                t.tw_off = tw.size();
+                t.w_off = wt.size();
+                for (int j = 0; j < t.n; ++j) {
+                    const double a = 2.0 * M_PI * (double)j / (double)t.n;
+                    tw.push_back(make_double2(std::cos(a), std::sin(a)));
+                }
+                t.kp = 0;
+                for (int j = 0; j < t.n; ++j) {
+                    const float jf = (float)j;
+                    const float g = 1.0f - std::exp(-(jf * jf) / den);
+                    const float wv = 1.0f - g;
+                    wt.push_back(wv);
+                    if (wv != 0.f) t.kp = j + 1;
+                }
+                t.kb = t.kp / 2 + 1;
+                t.R = 0;
+                for (int R : {4, 2, 1}) {
+                    const size_t lds = round16((size_t)t.n * 16 + (size_t)R * t.kb * 16 + (size_t)R * t.n * 4);
+                    // two blocks of four lines per CU (160 KB of LDS), three of two lines; one line when nothing else fits
+                    if (lds <= (R == 4 ? 80u : R == 2 ? 53u : 160u) * 1024u) { t.R = R; t.lds = lds; break; }
+                }
+                if (!t.R)
+                    return fail(MI_ERR_UNSUPPORTED, "mi_pystripe: a coefficient line of %d samples (sigma' = %g) does not fit the notch kernel's LDS",
+                                t.n, sp);
+                t.threads = std::min(512, std::max(64, (t.kb + 63) / 64 * 64));
+                P.tabs.push_back(t);
+            }
+    }
+    if (tw.empty()) return MI_OK;
+    MI_TRY(P.tw_buf.alloc(tw.size() * sizeof(double2)));
+    MI_TRY(P.w_buf.alloc(wt.size() * sizeof(float)));
+    MI_HIP(hipMemcpy(P.tw_buf.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
+    MI_HIP(hipMemcpy(P.w_buf.p, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice));
+    return MI_OK;
+}
+
+// The dynamic-LDS limit is an attribute of the kernel, not of a plan: it is set right before every launch that needs more than the
+// default, to that launch's own need (several plans of different shapes live side by side in batch_filter).
+template <int R>
+int launch_notch(const Plan& P, hipStream_t st, const NotchTab& t, float* c, i64 tile_stride, int nlines, i64 es, i64 ls, int cnt) {
+    const double2* tw = P.tw_buf.as<double2>() + t.tw_off;
+    const float* wt = P.w_buf.as<float>() + t.w_off;
+    if (t.lds > 48 * 1024)
+        MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&notch_kernel<R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds));
+    hipLaunchKernelGGL(notch_kernel<R>, dim3(cdiv(nlines, R), cnt), dim3(t.threads), t.lds, st, c, tile_stride, t.n, nlines, es, ls, tw, wt, t.kp,
+                       t.kb);
+    return launch_check("notch_kernel");
+}
+
+int run_notch(const Plan& P, hipStream_t st, const NotchTab& t, float* c, i64 tile_stride, int nlines, i64 es, i64 ls, int cnt) {
+    if (t.R == 4) return launch_notch<4>(P, st, t, c, tile_stride, nlines, es, ls, cnt);
+    if (t.R == 2) return launch_notch<2>(P, st, t, c, tile_stride, nlines, es, ls, cnt);
+    return launch_notch<1>(P, st, t, c, tile_stride, nlines, es, ls, cnt);
+}
+
+int run_chunk(Plan& P, hipStream_t st, const void* in, const float* flat, void* out, int cnt) {
+    const mi_pystripe_info& I = P.info;
+    const mi_pystripe_params& q = P.prm;
+    float* sc = P.scratch.as<float>();
+    const i64 cap = P.cap;
+    auto buf = [&](size_t off) { return sc + (i64)off * cap; };   // buffer b of all tiles: [tile][size_b]
+    int* varies = P.varies.as<int>();
+    const i64 npix = (i64)P.in_ny * P.in_nx;
+    MI_HIP(hipMemsetAsync(varies, q.keep_uniform ? 1 : 0, sizeof(int) * (size_t)cnt, st));
+    if (!q.keep_uniform && !q.log_output) {
+        if (P.in_dtype == MI_PS_U16) MI_TRY(launch_uniform<uint16_t>(st, in, npix, cnt, varies));
+        else if (P.in_dtype == MI_PS_U8) MI_TRY(launch_uniform<uint8_t>(st, in, npix, cnt, varies));
+        else MI_TRY(launch_uniform<float>(st, in, npix, cnt, varies));
+    }
+    Src src{in, npix, P.in_dtype, P.in_ny, P.in_nx, P.in_nx, 0, MAP_IDENTITY, 0};
+    if (P.pre) {
+        const int by = q.down_y > 0 ? q.down_y : 1, bx = q.down_x > 0 ? q.down_x : 1;
+        const dim3 grid(cdiv(I.nx, 64), cdiv(I.ny, 4), cnt);
+        hipLaunchKernelGGL(pre_kernel, grid, dim3(256), 0, st, src, q.use_flat ? flat : nullptr, by, bx, q.down_method, buf(P.off_stage), I.ny, I.nx);
+        MI_TRY(launch_check("pre_kernel"));
+        src = Src{buf(P.off_stage), (i64)P.sz_stage, MI_PS_F32, I.ny, I.nx, I.nx, 0, MAP_IDENTITY, 0};
+    }
+    Sink k{};
+    k.out = out;
+    k.tile_stride = (i64)I.out_ny * I.out_nx;
+    k.ny = I.ny; k.nx = I.nx; k.pad = I.base_pad;
+    k.filtered = P.filter; k.log_out = q.log_output; k.integer_kind = I.integer_kind;
+    k.in_max = P.in_dtype == MI_PS_U8 ? 255.f : 65535.f;
+    k.dark = q.dark;
+    const int cur = I.integer_kind ? P.in_dtype : MI_PS_F32;
+    k.out_dtype = I.out_dtype;
+    if (q.convert_to_16bit && cur != MI_PS_U16) { k.mode = OUT_CLIPCAST; k.cast_max = 65535.f; }
+    else if (q.convert_to_8bit && cur != MI_PS_U8) { k.mode = OUT_TO8; k.shift = q.bit_shift; }
+    else if (I.out_dtype != MI_PS_F32) { k.mode = OUT_CLIPCAST; k.cast_max = I.out_dtype == MI_PS_U8 ? 255.f : 65535.f; }
+    else k.mode = OUT_FLOAT;
+    k.flip = q.flip_upside_down; k.rot = q.rotate / 90;
+    k.varies = varies;
+    if (!P.filter) {
+        const dim3 grid(cdiv(I.nx, 64), cdiv(I.ny, 4), cnt);
+        hipLaunchKernelGGL(point_kernel, grid, dim3(256), 0, st, src, k);
+        return launch_check("point_kernel");
+    }
+    const int Lv = I.levels;
+    for (int pass = 0; pass < P.passes; ++pass) {
+        // analysis
+        for (int l = 1; l <= Lv; ++l) {
+            Src s;
+            int rows, map_mode = MAP_IDENTITY, map_pad = 0, map_rows = P.h[l - 1];
+            if (l == 1 && pass == 0) {
+                s = src;
+                s.pad = I.base_pad; s.mode = q.padding_mode; s.logp = 1;
+                rows = I.ny;
+                map_mode = q.padding_mode; map_pad = I.base_pad; map_rows = I.ny;
+            } else if (l == 1) {
+                s = Src{buf(P.off_P), (i64)P.sz_P, MI_PS_F32, P.h[0], P.w[0], P.w[0], 0, MAP_IDENTITY, 0};
+                rows = P.h[0];
+            } else {
+                s = Src{buf(P.off_A[l - 1]), (i64)P.sz_A[l - 1], MI_PS_F32, P.h[l - 1], P.w[l - 1], P.w[l - 1], 0, MAP_IDENTITY, 0};
+                rows = P.h[l - 1];
+            }
+            const int n = P.w[l - 1], m = P.w[l];
+            hipLaunchKernelGGL(ana_rows_kernel, dim3(cdiv(m, kRowBlock), rows, cnt), dim3(kRowBlock), 0, st, s, n, m, buf(P.off_rowL),
+                               buf(P.off_rowH), (i64)P.sz_row, P.f);
+            MI_TRY(launch_check("ana_rows_kernel"));
+            hipLaunchKernelGGL(ana_cols_kernel, dim3(cdiv(m, 64), cdiv(P.h[l], 4), cnt), dim3(256), 0, st, buf(P.off_rowL), buf(P.off_rowH),
+                               (i64)P.sz_row, P.h[l - 1], P.h[l], m, map_pad, map_rows, map_mode, buf(P.off_A[l]), (i64)P.sz_A[l],
+                               buf(P.off_cH[l]), buf(P.off_cV[l]), buf(P.off_cD[l]), (i64)P.sz_d[l], P.f);
+            MI_TRY(launch_check("ana_cols_kernel"));
+        }
+        // notch
+        for (int l = 1; l <= Lv; ++l) {
+            const NotchTab* t = &P.tabs[((size_t)pass * Lv + (l - 1)) * 2];
+            MI_TRY(run_notch(P, st, t[0], buf(P.off_cH[l]), (i64)P.sz_d[l], P.h[l], 1, P.w[l], cnt));
+            if (q.bidirectional) MI_TRY(run_notch(P, st, t[1], buf(P.off_cV[l]), (i64)P.sz_d[l], P.w[l], P.w[l], 1, cnt));
+        }
+        // synthesis, deepest level first; the reconstruction of level l lands in A[l - 1]'s buffer
+        const bool last_pass = pass == P.passes - 1;
+        for (int l = Lv; l >= 1; --l) {
+            const int m0 = P.h[l], m1 = P.w[l], s0 = 2 * m0 - 16, s1 = 2 * m1 - 16;
+            const float* a = buf(P.off_A[l]);
+            const int a_stride = l == Lv ? m1 : 2 * P.w[l + 1] - 16;
+            const bool fin = l == 1 && last_pass;
+            int y0 = 0, y1 = s0, xp0 = 0, xp1 = s1 / 2;
+            if (fin) {
+                y0 = I.base_pad; y1 = I.base_pad + I.ny;
+                xp0 = I.base_pad / 2; xp1 = (I.base_pad + I.nx + 1) / 2;
+            }
+            const int p0 = y0 / 2, p1 = (y1 + 1) / 2;
+            hipLaunchKernelGGL(syn_cols_kernel, dim3(cdiv(m1, 64), cdiv(p1 - p0, 4), 2 * cnt), dim3(256), 0, st, a, (i64)P.sz_A[l], a_stride,
+                               buf(P.off_cH[l]), buf(P.off_cV[l]), buf(P.off_cD[l]), (i64)P.sz_d[l], m1, p0, p1, s0, buf(P.off_rowL),
+                               buf(P.off_rowH), (i64)P.sz_row, P.f);
+            MI_TRY(launch_check("syn_cols_kernel"));
+            const dim3 grid(cdiv(xp1 - xp0, 256), y1 - y0, cnt);
+            if (fin) {
+                hipLaunchKernelGGL(syn_rows_kernel<true>, grid, dim3(256), 0, st, buf(P.off_rowL), buf(P.off_rowH), (i64)P.sz_row, m1, y0, xp0, xp1,
+                                   s1, (float*)nullptr, (i64)0, k, P.f);
+            } else {
+                float* dst = l == 1 ? buf(P.off_P) : buf(P.off_A[l - 1]);
+                const i64 dst_stride = l == 1 ? (i64)P.sz_P : (i64)P.sz_A[l - 1];
+                hipLaunchKernelGGL(syn_rows_kernel<false>, grid, dim3(256), 0, st, buf(P.off_rowL), buf(P.off_rowH), (i64)P.sz_row, m1, y0, xp0, xp1,
+                                   s1, dst, dst_stride, k, P.f);
+            }
+            MI_TRY(launch_check("syn_rows_kernel"));
+        }
+    }
+    return MI_OK;
+}
+
+}  // namespace
+}  // namespace mi
+
+using mi::Plan;
+
+extern "C" int mi_pystripe_pad_size(int ny, int nx, double sigma) {
+    if (ny <= 0 || nx <= 0 || sigma < 0) return mi::fail(MI_ERR_INVALID, "mi_pystripe_pad_size: shape (%d, %d), sigma %g", ny, nx, sigma);
+    return mi::pad_size(ny, nx, sigma);
+}
+
+extern "C" int mi_pystripe_derive(int ny, int nx, int in_dtype, const mi_pystripe_params* params, mi_pystripe_info* info) {
+    MI_REQUIRE(params && info, "mi_pystripe_derive: null pointer");
+    Plan P;
+    MI_TRY(mi::derive(ny, nx, in_dtype, *params, P));
+    *info = P.info;
+    return MI_OK;
+}
+
+extern "C" int mi_pystripe_plan_create(int dev, int ny, int nx, int in_dtype, const mi_pystripe_params* params, void** plan) {
+    MI_REQUIRE(params && plan, "mi_pystripe_plan_create: null pointer");
+    *plan = nullptr;
+    MI_TRY(mi::use_device(dev));
+    Plan* P = new Plan;
+    P->dev = dev;
+    P->f = mi::make_filters();
+    int rc = mi::derive(ny, nx, in_dtype, *params, *P);
+    if (rc == MI_OK) rc = mi::build_tables(*P);
+    if (rc != MI_OK) {
+        delete P;
+        return rc;
+    }
+    *plan = P;
+    return MI_OK;
+}
+
+extern "C" int mi_pystripe_plan_destroy(void* plan) {
+    if (!plan) return MI_OK;
+    Plan* P = static_cast<Plan*>(plan);
+    const int rc = mi::use_device(P->dev);
+    delete P;
+    return rc;
+}
+
+extern "C" int mi_pystripe_plan_info(void* plan, mi_pystripe_info* info) {
+    MI_REQUIRE(plan && info, "mi_pystripe_plan_info: null pointer");
+    *info = static_cast<Plan*>(plan)->info;
+    return MI_OK;
+}
+
+extern "C" int mi_pystripe_run(void* plan, void* stream, const void* in, const void* flat, void* out, int64_t count) {
+    MI_REQUIRE(plan && in && out, "mi_pystripe_run: null pointer");
+    MI_REQUIRE(count >= 0, "mi_pystripe_run: count %lld", (long long)count);
+    Plan& P = *static_cast<Plan*>(plan);
+    MI_REQUIRE(!P.prm.use_flat || flat, "mi_pystripe_run: the plan divides by a flat field and none is given");
+    if (count == 0) return MI_OK;
+    MI_TRY(mi::use_device(P.dev));
+    hipStream_t st = mi::as_stream(stream);
+    const int64_t want = std::min<int64_t>(count, P.info.max_batch);
+    if (want > P.cap) {
+        // work of an earlier call may still use the smaller scratch
+        MI_HIP(hipStreamSynchronize(st));
+        P.cap = 0;
+        MI_TRY(P.scratch.alloc(std::max<size_t>(P.info.scratch_bytes_per_tile * (size_t)want, 16)));
+        MI_TRY(P.varies.alloc(sizeof(int) * (size_t)want));
+        P.cap = want;
+    }
+    const size_t in_bytes = (size_t)P.in_ny * P.in_nx * (P.in_dtype == MI_PS_U8 ? 1 : P.in_dtype == MI_PS_U16 ? 2 : 4);
+    const size_t out_bytes = (size_t)P.info.out_ny * P.info.out_nx * (P.info.out_dtype == MI_PS_U8 ? 1 : P.info.out_dtype == MI_PS_U16 ? 2 : 4);
+    for (int64_t t0 = 0; t0 < count; t0 += P.cap) {
+        const int cnt = (int)std::min<int64_t>(P.cap, count - t0);
+        MI_TRY(mi::run_chunk(P, st, static_cast<const char*>(in) + (size_t)t0 * in_bytes, static_cast<const float*>(flat),
+                             static_cast<char*>(out) + (size_t)t0 * out_bytes, cnt));
+    }
+    return MI_OK;
+}

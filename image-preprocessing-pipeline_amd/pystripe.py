@@ -1,0 +1,629 @@
+#!/usr/bin/env python3
+"""pystripe tile preprocessing on the GPU: ``pystripe.core`` of the reference for the options ``process_images.py`` uses
+(``process_images.py:420-447`` on raw tiles, ``:702-724`` on merged slices).
+
+    from ipp_amd.pystripe import batch_filter
+    batch_filter(input_path, output_path, sigma=(250, 250), wavelet="db9", padding_mode="reflect", bidirectional=True, ...)
+
+``batch_filter`` is the drop-in boundary: the reference's keyword names and defaults, returns 0.  ``process_img`` and
+``filter_streaks`` take one 2-D tile (numpy array or device tensor) like the reference, or a stack ``[n, ny, nx]`` of equally shaped
+tiles, which go through every kernel launch together (include/mi_pystripe.h).  There is no CPU path: a missing library or device is
+an error.
+
+What is computed (reference line numbers in include/mi_pystripe.h): uniform tile -> zeros; flat field; ``down_sample`` (max / min /
+mean, zero-padded blocks like skimage's ``block_reduce``); ``filter_streaks`` = log1p, numpy padding (reflect / wrap / symmetric /
+edge), db9 wavelet decomposition, the packed-position Gaussian notch on cH (and cV when ``bidirectional``), reconstruction, crop,
+expm1, rint + clip for integer tiles; ``dark``; 8 / 16-bit conversion; flip; rotation.
+
+Departures, all stated in INTEGRATION.md:
+  * ``flat`` on an integer tile: the reference's in-place divide raises; here the tile is divided in float32 and is a float tile from
+    there on (the float32-tile case matches the reference);
+  * ``gaussian_filter_2d`` is accepted and does nothing, as in the reference (its GaussianBlur result is discarded);
+  * refused by name: ``bleach_correction_frequency``, ``enable_masking``, ``lightsheet``, ``exclude_dark_edges_set_them_to_zero``,
+    ``new_size``, ``.dcimg`` input, ``down_sample_method='median'``, wavelets other than ``db9``, other padding modes, a ``threshold``
+    (``use_thresholding`` is never set on this path; ``crossover`` has no effect there either);
+  * accepted and ignored: ``workers``, ``threads_per_gpu``, ``timeout``, ``gpu_semaphore``, ``z_step``, ``print_input_file_names``,
+    ``verbose`` and the lightsheet tuning numbers.
+The command line takes the reference's LONG option names with plain ``store_true`` flags; the reference's own parser cannot be built
+(``-w`` is given to two options), so the CLI is not claimed as a byte-for-byte drop-in.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import os
+import sys
+import warnings
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
+
+import numpy as np
+
+if __package__ in (None, ""):
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    __package__ = "ipp_amd"
+
+from . import capi  # noqa: E402
+
+_NP_CODES = {np.dtype(np.uint8): capi.PS_U8, np.dtype(np.uint16): capi.PS_U16, np.dtype(np.float32): capi.PS_F32}
+_CODE_NP = {v: k for k, v in _NP_CODES.items()}
+SUPPORTED_EXTENSIONS = (".tif", ".tiff", ".raw", ".png")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# small host functions of the reference
+
+def calculate_pad_size(shape, sigma, rise=0.5):
+    """Rows / columns of padding around a tile of ``shape`` = (ny, nx) for a notch of width ``sigma`` (what pystripe/core.py:681 and
+    :670 compute; ``mi_pystripe_pad_size`` is the same in C).  The Gaussian notch ``1 - exp(-j^2 / (2 sigma^2))`` reaches the level
+    ``r`` at ``j = sigma * sqrt(-2 ln(1 - r))``; the pad is that distance rounded to the nearest integer and then down to an even
+    one.  ``r`` is ``rise`` unless the reference's memory bound is lower: with ``u = nx + 1``, ``v = ny + 1`` and the budget 5e14,
+    ``1 - exp((u + v - sqrt((u - v)^2 + 4 * 5e14)) / (4 sigma^2))`` rounded to two decimals, less 0.01."""
+    if not sigma:
+        return 0
+    u, v, budget = shape[1] + 1, shape[0] + 1, 5e14
+    exponent = (u + v - math.sqrt((u - v) ** 2 + 4 * budget)) / (4 * sigma ** 2)
+    level = min(rise, round(1 - math.exp(exponent), 2) - 0.01)
+    reach = math.sqrt(-2 * sigma ** 2 * math.log(1 - level))
+    return 2 * (int(reach + 0.5) // 2)
+
+
+def calculate_down_sampled_size(tile_size, down_sample):
+    """Shape after ``down_sample``: every extent divided by its block, rounded up (pystripe/core.py:1162)."""
+    return tuple(int(s) if d is None else -(-int(s) // int(d)) for s, d in zip(tile_size, down_sample))
+
+
+def normalize_flat(flat):
+    """The flat field as float32 with its largest value scaled to 1 (pystripe/core.py:2047)."""
+    out = np.array(flat, dtype=np.float32)
+    np.divide(out, out.max(), out=out)
+    return out
+
+
+def convert_to_16bit_fun(img):
+    """Values limited to 0 .. 65535, then truncated to uint16 (pystripe/core.py:397)."""
+    return np.minimum(np.maximum(img, 0), 65535).astype(np.uint16)
+
+
+def convert_to_8bit_fun(img, bit_shift_to_right=8):
+    """A uint16 image (anything else goes through ``convert_to_16bit_fun`` first) shifted right by 0 .. 8 bits and limited to 255; a
+    value that is not zero never becomes zero: it becomes 1 (pystripe/core.py:402).  uint8 input is returned as it is.  Host arrays;
+    the device path does the same inside its store."""
+    shift = 8 if bit_shift_to_right is None else int(bit_shift_to_right)
+    if img is None or img.dtype == np.uint8:
+        return img
+    if shift not in range(9):
+        raise RuntimeError(f"right shift should be between 0 and 8 (bit_shift_to_right={bit_shift_to_right})")
+    wide = img if img.dtype == np.uint16 else convert_to_16bit_fun(img)
+    out = np.minimum(wide >> shift, 255).astype(np.uint8)
+    out[(wide > 0) & (out == 0)] = 1
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# options -> mi_pystripe_params
+
+def _refuse(name, value, why):
+    raise NotImplementedError(f"{name}={value!r}: {why}")
+
+
+def _check_unsupported(kw):
+    """Raises NotImplementedError naming the first option this build does not do."""
+    if kw.get("bleach_correction_frequency") is not None:
+        _refuse("bleach_correction_frequency", kw["bleach_correction_frequency"], "bleach correction is not built")
+    for name in ("enable_masking", "lightsheet", "exclude_dark_edges_set_them_to_zero"):
+        if kw.get(name):
+            _refuse(name, kw[name], "not built (needs OpenCV / scikit-image semantics)")
+    if kw.get("new_size") is not None:
+        _refuse("new_size", kw["new_size"], "skimage.transform.resize is not built")
+    if kw.get("threshold") is not None:
+        _refuse("threshold", kw["threshold"], "the thresholding dual-band path is not built")
+    if kw.get("log1p_normalization_needed") is False:
+        _refuse("log1p_normalization_needed", False, "only the log1p path is built")
+
+
+def _sigma_pair(sigma):
+    """(sigma1, sigma2) as floats; a single number stands for both."""
+    try:
+        first, second = sigma
+    except TypeError:
+        first = second = sigma
+    return float(first), float(second)
+
+
+def _dtype_code(dt, what):
+    dt = np.dtype(dt)
+    if dt not in _NP_CODES:
+        raise TypeError(f"{what}={dt.name}: uint8, uint16 and float32 are built")
+    return _NP_CODES[dt]
+
+
+def make_params(in_dtype, flat=False, down_sample=None, down_sample_method="max", sigma=(0, 0), level=0, wavelet="db9",
+                padding_mode="reflect", bidirectional=False, dark=0, rotate=0, flip_upside_down=False, convert_to_16bit=False,
+                convert_to_8bit=False, bit_shift_to_right=8, d_type=None, log_output=False, keep_uniform=False, max_batch=0):
+    """mi_pystripe_params for process_img's options.  Everything the C side cannot name itself is refused here."""
+    s1, s2 = _sigma_pair(sigma)
+    filt = (s1, s2) > (0, 0)
+    if filt:
+        if wavelet != "db9":
+            _refuse("wavelet", wavelet, "only 'db9' is built (the pipeline's choice)")
+        if (s1 > 0) != (s2 > 0) or s1 < 0 or s2 < 0:
+            raise ValueError(f"np_notch: sigma must be positive (sigma={sigma!r})")
+        mode = padding_mode.lower() if isinstance(padding_mode, str) else padding_mode
+        if mode not in capi.PS_PADDING:
+            if mode in ("constant", "linear_ramp", "maximum", "mean", "median", "minimum", "empty"):
+                _refuse("padding_mode", padding_mode, "reflect, wrap, symmetric and edge are built")
+            print(f"Unsupported padding mode: {padding_mode}")
+            raise RuntimeError(f"Unsupported padding mode: padding_mode={padding_mode!r}")
+    else:
+        s1 = s2 = 0.0
+        mode = "reflect"
+    p = capi.PystripeParams()
+    p.sigma1, p.sigma2, p.level = s1, s2, int(level)
+    p.padding_mode = capi.PS_PADDING[mode]
+    p.bidirectional = int(bool(bidirectional))
+    if down_sample is not None:
+        method = str(down_sample_method).lower()
+        if method == "median":
+            _refuse("down_sample_method", down_sample_method, "max, min and mean are built")
+        if method not in capi.PS_DOWN:
+            print(f"unsupported down-sampling method: {down_sample_method}")
+            raise RuntimeError(f"unsupported down-sampling method: down_sample_method={down_sample_method!r}")
+        p.down_y, p.down_x = (int(d) if d is not None else 1 for d in down_sample)
+        p.down_method = capi.PS_DOWN[method]
+    p.use_flat = int(bool(flat))
+    p.dark = float(dark) if dark is not None and dark > 0 else 0.0
+    if convert_to_16bit and convert_to_8bit:
+        raise TypeError("convert_to_16bit and convert_to_8bit are both set")
+    bit_shift_to_right = 8 if bit_shift_to_right is None else bit_shift_to_right
+    if convert_to_8bit and bit_shift_to_right not in range(9):
+        raise RuntimeError(f"right shift should be between 0 and 8 (bit_shift_to_right={bit_shift_to_right})")
+    p.convert_to_16bit, p.convert_to_8bit, p.bit_shift = int(bool(convert_to_16bit)), int(bool(convert_to_8bit)), int(bit_shift_to_right)
+    if rotate not in (0, 90, 180, 270):
+        rotate = 0   # the reference rotates for 90 / 180 / 270 and leaves every other value alone
+    p.rotate, p.flip_upside_down = int(rotate), int(bool(flip_upside_down))
+    if convert_to_16bit:
+        out = np.uint16
+    elif convert_to_8bit:
+        out = np.uint8
+    else:
+        out = in_dtype if d_type is None else d_type
+    p.out_dtype = _dtype_code(out, "d_type")
+    p.log_output, p.keep_uniform, p.max_batch = int(bool(log_output)), int(bool(keep_uniform)), int(max_batch)
+    return p
+
+
+def derive(shape, in_dtype, params):
+    """The bookkeeping of a plan without a device (pad, padded shape, levels, coefficient shapes, output shape and type)."""
+    info = capi.PystripeInfo()
+    capi.check(capi.lib().mi_pystripe_derive(int(shape[0]), int(shape[1]), _dtype_code(in_dtype, "dtype"), C.byref(params), C.byref(info)))
+    return info
+
+
+class Plan:
+    """mi_pystripe plan for tiles of one shape and dtype.  ``run(tiles[, flat])``: [n, ny, nx] device tensor -> result tensor."""
+
+    def __init__(self, device, shape, in_dtype, params):
+        import torch
+        capi.require_gpu()
+        self.device = torch.device(device if device is not None else "cuda:0")
+        self.shape, self.in_dtype, self.params = (int(shape[0]), int(shape[1])), np.dtype(in_dtype), params
+        self._h = C.c_void_p()
+        capi.check(capi.lib().mi_pystripe_plan_create(self.device.index or 0, self.shape[0], self.shape[1], _dtype_code(in_dtype, "dtype"),
+                                                      C.byref(params), C.byref(self._h)))
+        self.info = capi.PystripeInfo()
+        capi.check(capi.lib().mi_pystripe_plan_info(self._h, C.byref(self.info)))
+        self.out_shape = (self.info.out_ny, self.info.out_nx)
+        self.out_dtype = _CODE_NP[self.info.out_dtype]
+
+    def run(self, tiles, flat=None, out=None):
+        import torch
+        tdt = getattr(torch, self.in_dtype.name)
+        if not (isinstance(tiles, torch.Tensor) and tiles.is_cuda and tiles.is_contiguous() and tiles.dim() == 3 and tiles.dtype == tdt
+                and tuple(tiles.shape[1:]) == self.shape):
+            raise ValueError(f"Plan.run: a contiguous [n, {self.shape[0]}, {self.shape[1]}] {self.in_dtype.name} device tensor is expected")
+        n = int(tiles.shape[0])
+        if out is None:
+            out = torch.empty((n,) + self.out_shape, dtype=getattr(torch, self.out_dtype.name), device=tiles.device)
+        fp = None
+        if self.params.use_flat:
+            if flat is None or tuple(flat.shape) != self.shape or flat.dtype != torch.float32 or not flat.is_contiguous():
+                raise ValueError("Plan.run: the plan divides by a flat field: a contiguous float32 tensor of the tile's shape is expected")
+            fp = flat.data_ptr()
+        with torch.cuda.device(tiles.device):
+            capi.check(capi.lib().mi_pystripe_run(self._h, capi.current_stream_ptr(tiles.device), tiles.data_ptr(), fp, out.data_ptr(), n))
+        return out
+
+    def close(self):
+        if self._h:
+            capi.lib().mi_pystripe_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _run_tiles(img, flat, device, **opts):
+    """img: 2-D tile or [n, ny, nx] stack, numpy or device tensor -> the same kind of container."""
+    import torch
+    is_tensor = isinstance(img, torch.Tensor)
+    if is_tensor:
+        tiles = img
+        in_dtype = np.dtype(str(img.dtype).replace("torch.", ""))
+    else:
+        img = np.asarray(img)
+        in_dtype = img.dtype
+        _dtype_code(in_dtype, "img.dtype")
+        capi.require_gpu()
+        tiles = torch.from_numpy(np.ascontiguousarray(img)).to(torch.device(device if device is not None else "cuda:0"))
+    single = tiles.dim() == 2
+    if tiles.dim() not in (2, 3):
+        raise ValueError(f"a 2-D tile or a stack [n, ny, nx] is expected, got shape {tuple(tiles.shape)}")
+    tiles = (tiles[None] if single else tiles).contiguous()
+    shape = tuple(int(v) for v in tiles.shape[1:])
+    flat_t = None
+    if flat is not None:
+        if tuple(flat.shape) == shape:
+            flat_t = flat if isinstance(flat, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(flat, dtype=np.float32))
+            flat_t = flat_t.to(tiles.device, torch.float32).contiguous()
+        else:
+            warnings.warn("warning: image and flat arrays had different shapes")
+    params = make_params(in_dtype, flat=flat_t is not None, max_batch=min(int(tiles.shape[0]), 16), **opts)
+    plan = Plan(tiles.device, shape, in_dtype, params)
+    try:
+        out = plan.run(tiles, flat_t)
+        torch.cuda.synchronize(tiles.device)
+    finally:
+        plan.close()
+    out = out[0] if single else out
+    return out if is_tensor else out.cpu().numpy()
+
+
+def filter_streaks(img, sigma=(250, 250), level=0, wavelet="db9", crossover=10, threshold=None, padding_mode="wrap",
+                   bidirectional=False, gpu_semaphore=None, bleach_correction_frequency=None, bleach_correction_max_method=False,
+                   bleach_correction_clip_min=None, bleach_correction_clip_med=None, bleach_correction_clip_max=None,
+                   log1p_normalization_needed=True, enable_masking=False, close_steps=50, open_steps=500, verbose=False, device=None,
+                   log_output=False):
+    """pystripe/core.py:982 on the GPU.  ``crossover`` has no effect on this path (as in the reference).  ``log_output=True`` returns
+    the float32 image just before ``expm1`` (an addition, for tests)."""
+    _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, enable_masking=enable_masking, threshold=threshold,
+                            log1p_normalization_needed=log1p_normalization_needed))
+    s1, s2 = _sigma_pair(sigma)
+    if s1 == s2 == 0:
+        return img
+    return _run_tiles(img, None, device, sigma=(s1, s2), level=level, wavelet=wavelet, padding_mode=padding_mode, bidirectional=bidirectional,
+                      keep_uniform=True, log_output=log_output)
+
+
+def process_img(img, flat=None, gaussian_filter_2d=False, down_sample=None, down_sample_method="max", tile_size=None, new_size=None,
+                exclude_dark_edges_set_them_to_zero=False, sigma=(0, 0), level=0, wavelet="coif15", crossover=10, threshold=None,
+                padding_mode="wrap", bidirectional=False, gpu_semaphore=None, bleach_correction_frequency=None,
+                bleach_correction_clip_min=None, bleach_correction_clip_med=None, bleach_correction_clip_max=None,
+                bleach_correction_max_method=False, log1p_normalization_needed=True, dark=0, lightsheet=False, artifact_length=150,
+                background_window_size=200, percentile=0.25, lightsheet_vs_background=2.0, rotate=0, flip_upside_down=False,
+                convert_to_16bit=False, convert_to_8bit=False, bit_shift_to_right=8, d_type=None, verbose=False, device=None):
+    """pystripe/core.py:1190 on the GPU, the reference's keywords and defaults (so ``wavelet`` must be given as 'db9' when ``sigma`` asks
+    for the filter).  ``gaussian_filter_2d`` does nothing, as in the reference, whose GaussianBlur result is discarded.  ``img`` may be
+    a stack [n, ny, nx] of equally shaped tiles (an addition): they go through every launch together."""
+    _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, lightsheet=lightsheet, new_size=new_size,
+                            exclude_dark_edges_set_them_to_zero=exclude_dark_edges_set_them_to_zero, threshold=threshold,
+                            log1p_normalization_needed=log1p_normalization_needed))
+    return _run_tiles(img, flat, device, down_sample=down_sample, down_sample_method=down_sample_method, sigma=sigma, level=level,
+                      wavelet=wavelet, padding_mode=padding_mode, bidirectional=bidirectional, dark=dark, rotate=rotate,
+                      flip_upside_down=flip_upside_down, convert_to_16bit=convert_to_16bit, convert_to_8bit=convert_to_8bit,
+                      bit_shift_to_right=bit_shift_to_right, d_type=d_type)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# folder -> folder
+
+def find_tiles(path, extensions=SUPPORTED_EXTENSIONS):
+    """Every file under ``path``, at any depth, whose suffix is one of ``extensions`` in either letter case -- the files the
+    reference's ``glob_re`` walk (pystripe/core.py:1603) hands to batch_filter.  Directories reached through links are not entered."""
+    found = []
+    for folder, _, names in os.walk(path, followlinks=False):
+        found.extend(Path(folder) / name for name in names if os.path.splitext(name)[1].lower() in extensions)
+    return sorted(found)
+
+
+def raw_imread(path):
+    """tsv/raw.py:9: 8-byte header (width, height as uint32, endianness by the smaller width), uint16 samples."""
+    head = np.fromfile(path, dtype=np.uint8, count=8)
+    w_be, h_be = head.view(">u4")
+    w_le, h_le = head.view("<u4")
+    (w, h, dt) = (w_le, h_le, "<u2") if w_le < w_be else (w_be, h_be, ">u2")
+    return np.fromfile(path, dtype=dt, offset=8, count=int(w) * int(h)).reshape(int(h), int(w)).astype(np.uint16)
+
+
+def imread_tif_raw_png(path, dtype=None, shape=None):
+    """One tile, or None when the file cannot be read (pystripe/core.py:200 without its repair attempts).  TIFFs the library's reader
+    takes go through it (mi_tiffio.h); every other TIFF and PNG through Pillow."""
+    from . import brickio
+    path = Path(path)
+    ext = path.suffix.lower()
+    try:
+        if ext == ".raw":
+            return raw_imread(path)
+        if ext == ".dcimg":
+            _refuse("input", path.name, ".dcimg input is not built")
+        if ext in (".tif", ".tiff"):
+            info = brickio.tiff_info(path)
+            if info is not None and info[2] and info[1] is not None:
+                (ny, nx), dt, _ = info
+                return brickio.read_tiff_box([path], (ny, nx), dt, 0, ny, 0, nx)[0]
+        if ext in (".tif", ".tiff", ".png"):
+            from PIL import Image
+            with Image.open(path) as handle:
+                return np.asarray(handle).copy()
+        print(f"Unsupported file format: {ext}")
+    except NotImplementedError:
+        raise
+    except Exception as e:   # a damaged file: the caller decides (zero tile or skip)
+        print(f"file: {path.name} failed to read: {type(e).__name__} - {e}")
+    return None
+
+
+def imsave_tif(path, img, compression=("ADOBE_DEFLATE", 1)):
+    """One 2-D TIFF with the library's writer (Adobe deflate at the given level, or uncompressed)."""
+    _write_tiles([Path(path)], np.ascontiguousarray(img)[None], compression)
+    return True
+
+
+def _write_tiles(paths, stack, compression):
+    lib = capi.lib()
+    n = len(paths)
+    for p in paths:
+        p.parent.mkdir(parents=True, exist_ok=True)
+        if p.exists():
+            p.unlink()       # the writer leaves an existing file alone; here the caller has already decided to replace it
+    level = 1
+    comp = 1
+    if compression is None:
+        comp = 0
+    elif str(compression[0]).upper() not in ("ADOBE_DEFLATE", "DEFLATE", "ZLIB"):
+        _refuse("compression", compression, "ADOBE_DEFLATE or None")
+    else:
+        level = min(max(int(compression[1]), 1), 9)
+    code = {np.dtype(np.uint8): 1, np.dtype(np.uint16): 2, np.dtype(np.float32): 4}[stack.dtype]
+    arr = (C.c_char_p * n)(*[os.fsencode(str(p)) for p in paths])
+    capi.check(lib.mi_tiff_write_series(arr, n, stack.ctypes.data, code, stack.shape[2], stack.shape[1], comp, level, 0, None))
+
+
+def split_for_rank(files, rank=None, world=None):
+    """The share of ``files`` of this torchrun rank (RANK / WORLD_SIZE): every world-th file, so the ranks cover every file once."""
+    rank = int(os.environ.get("RANK", 0)) if rank is None else int(rank)
+    world = int(os.environ.get("WORLD_SIZE", 1)) if world is None else int(world)
+    return list(files)[rank::world] if world > 1 else list(files)
+
+
+def batch_filter(input_path, output_path, files_list=None, workers=None, threads_per_gpu=8, flat=None, gaussian_filter_2d=False,
+                 sigma=(0, 0), level=0, wavelet="db9", crossover=10, threshold=None, padding_mode="reflect", bidirectional=False,
+                 bleach_correction_frequency=None, bleach_correction_max_method=True, bleach_correction_clip_min=None,
+                 bleach_correction_clip_med=None, bleach_correction_clip_max=None, dark=0, z_step=None, rotate=0, flip_upside_down=False,
+                 lightsheet=False, artifact_length=150, background_window_size=200, percentile=.25, lightsheet_vs_background=2.0,
+                 convert_to_16bit=False, convert_to_8bit=False, bit_shift_to_right=8, continue_process=False, d_type=None, tile_size=None,
+                 down_sample=None, new_size=None, print_input_file_names=False, timeout=None, compression=("ADOBE_DEFLATE", 1),
+                 down_sample_method="max", device=None, max_batch=None, stats=None):
+    """pystripe/core.py:1806: every .tif / .tiff / .raw / .png under ``input_path`` (or ``files_list``) -> the same relative path
+    under ``output_path`` with a ``.tif`` suffix.  Returns 0.
+
+    Tiles of equal shape and dtype are grouped into batches sized from the free device memory (``max_batch`` overrides); the next
+    batch is read and the previous one written on host threads while the device works on the current one.  Under ``torchrun`` every
+    rank takes every WORLD_SIZE-th file on its LOCAL_RANK device.  ``continue_process``: a file whose output exists is skipped.  A file
+    that cannot be read becomes a zero tile when ``d_type`` and ``tile_size`` are given, else it is skipped with a warning.
+    ``workers``, ``threads_per_gpu``, ``timeout``, ``z_step``, ``print_input_file_names`` are accepted and ignored.  ``stats`` (a dict)
+    receives the seconds spent reading, computing and writing and the file counts."""
+    import time
+    import torch
+    if convert_to_16bit and convert_to_8bit:
+        raise TypeError("convert_to_16bit and convert_to_8bit are both set: choose one output format")
+    _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, lightsheet=lightsheet, new_size=new_size,
+                            threshold=threshold))
+    input_path, output_path = Path(input_path), Path(output_path)
+    if input_path.suffix.lower() == ".dcimg":
+        _refuse("input_path", str(input_path), ".dcimg input is not built")
+    if files_list is None:
+        if input_path.is_file():
+            files_list, input_path = [input_path], input_path.parent
+        else:
+            files_list = find_tiles(input_path)
+    files = [Path(f) if Path(f).is_absolute() or Path(f).exists() else input_path / f for f in files_list]
+    files = split_for_rank(files)
+    capi.require_gpu()
+    if device is None:
+        device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)) % max(torch.cuda.device_count(), 1))
+    device = torch.device(device)
+    if flat is not None:
+        flat = normalize_flat(flat)
+    if tile_size is not None:
+        tile_size = tuple(int(v) for v in tile_size)
+    opts = dict(down_sample=down_sample, down_sample_method=down_sample_method, sigma=sigma, level=level, wavelet=wavelet,
+                padding_mode=padding_mode, bidirectional=bidirectional, dark=dark, rotate=rotate, flip_upside_down=flip_upside_down,
+                convert_to_16bit=convert_to_16bit, convert_to_8bit=convert_to_8bit, bit_shift_to_right=bit_shift_to_right, d_type=d_type)
+
+    st = dict(read_s=0.0, compute_s=0.0, write_s=0.0, files=len(files), written=0, skipped_existing=0, skipped_unreadable=0, zero_tiles=0)
+    todo = []
+    for f in files:
+        try:
+            rel = f.relative_to(input_path)
+        except ValueError:
+            rel = Path(f.name)
+        o = (output_path / rel).with_suffix(".tif")
+        if continue_process and o.exists():
+            st["skipped_existing"] += 1
+            continue
+        todo.append((f, o))
+
+    def read_many(paths):
+        """{path: tile}: the TIFFs the library's reader takes go through it together (one call decodes them on all cores); what is left
+        -- other TIFFs, .raw, .png, and every file of a call that failed -- is read one by one."""
+        from . import brickio
+        got, kinds = {}, {}
+        for f in paths:
+            if f.suffix.lower() in (".tif", ".tiff"):
+                info = brickio.tiff_info(f)
+                if info is not None and info[2] and info[1] is not None:
+                    kinds.setdefault((info[0], np.dtype(info[1])), []).append(f)
+        for ((ny, nx), dt), fs in kinds.items():
+            try:
+                stack = brickio.read_tiff_box(fs, (ny, nx), dt, 0, ny, 0, nx)
+                got.update(zip(fs, stack))
+            except Exception:   # a damaged file among them: the one-by-one route finds it
+                pass
+        for f in paths:
+            if f not in got:
+                got[f] = imread_tif_raw_png(f, dtype=d_type, shape=tile_size)
+        return got
+
+    def read_group(items):
+        t0 = time.perf_counter()
+        out = []
+        tiles = read_many([f for f, _ in items])
+        for f, o in items:
+            img = tiles[f]
+            if img is not None and (img.ndim != 2 or img.dtype not in _NP_CODES):
+                print(f"file: {f.name}: a 2-D uint8 / uint16 / float32 image is expected, got {img.dtype} {img.shape}")
+                img = None
+            can_substitute = d_type is not None and tile_size is not None
+            if img is None and can_substitute:
+                print(f"warning: could not read {f}: the output is a dummy zeros tile of shape {tile_size} and type {d_type}")
+                img = np.zeros(tile_size, np.dtype(d_type))
+                st["zero_tiles"] += 1
+            elif img is None:
+                print(f"warning: could not read {f}: skipped (a dummy tile of zeros needs tile_size and d_type)")
+                st["skipped_unreadable"] += 1
+                continue
+            out.append((img, o))
+        st["read_s"] += time.perf_counter() - t0
+        return out
+
+    def write_group(paths, stack):
+        t0 = time.perf_counter()
+        _write_tiles(paths, stack, compression)
+        st["write_s"] += time.perf_counter() - t0
+        st["written"] += len(paths)
+
+    plans = {}
+
+    def compute(group):
+        """tiles of one read group, any mix of shapes -> [(paths, host stack)]"""
+        t0 = time.perf_counter()
+        by_kind = {}
+        for img, o in group:
+            by_kind.setdefault((img.shape, img.dtype), []).append((img, o))
+        results = []
+        for (shape, dt), members in by_kind.items():
+            use_flat = flat is not None and flat.shape == shape
+            if flat is not None and not use_flat:
+                print("warning: image and flat arrays had different shapes")
+            key = (shape, dt, use_flat)
+            if key not in plans:
+                prm = make_params(dt, flat=use_flat, max_batch=chunk, **opts)
+                plans[key] = (Plan(device, shape, dt, prm), torch.from_numpy(flat).to(device) if use_flat else None)
+            plan, flat_t = plans[key]
+            stack = torch.from_numpy(np.stack([m[0] for m in members])).to(device)
+            out = plan.run(stack, flat_t).cpu().numpy()
+            results.append(([m[1] for m in members], out))
+        st["compute_s"] += time.perf_counter() - t0
+        return results
+
+    # batch size: the scratch of a batch plus its input and output must fit a quarter of the free device memory
+    chunk = 16
+    if max_batch is not None:
+        chunk = max(int(max_batch), 1)
+    elif todo:
+        first = imread_tif_raw_png(todo[0][0]) if tile_size is None else np.zeros(tile_size, np.dtype(d_type or np.uint16))
+        if first is not None and first.ndim == 2 and first.dtype in _NP_CODES:
+            info = derive(first.shape, first.dtype, make_params(first.dtype, flat=False, **opts))
+            per_tile = info.scratch_bytes_per_tile + 2 * first.size * 4
+            with torch.cuda.device(device):
+                free = torch.cuda.mem_get_info()[0]
+            chunk = int(min(max(free // 4 // max(per_tile, 1), 1), 64))
+    groups = [todo[i:i + chunk] for i in range(0, len(todo), chunk)]
+    with ThreadPoolExecutor(1) as reader, ThreadPoolExecutor(1) as writer:
+        pending_writes = []
+        nxt = reader.submit(read_group, groups[0]) if groups else None
+        for gi in range(len(groups)):
+            group = nxt.result()
+            nxt = reader.submit(read_group, groups[gi + 1]) if gi + 1 < len(groups) else None
+            for paths, stack in compute(group):
+                pending_writes.append(writer.submit(write_group, paths, stack))
+            while len(pending_writes) > 2:
+                pending_writes.pop(0).result()
+        for w in pending_writes:
+            w.result()
+    for plan, _ in plans.values():
+        plan.close()
+    if stats is not None:
+        stats.update(st)
+    return 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# command line
+
+def _parse_args(argv=None):
+    import argparse
+    p = argparse.ArgumentParser(prog="pystripe.py", allow_abbrev=False,
+                                description="pystripe tile preprocessing on the GPU (the reference's long option names, plain store_true flags)")
+    p.add_argument("--input", "-i", required=True, help="folder (searched recursively) or one image file")
+    p.add_argument("--output", "-o", default="", help="output folder (default: <input>_destriped)")
+    p.add_argument("--sigma1", "-s1", type=float, default=0, help="foreground bandwidth [pixels]")
+    p.add_argument("--sigma2", "-s2", type=float, default=0, help="background bandwidth [pixels]")
+    p.add_argument("--level", "-l", type=int, default=0)
+    p.add_argument("--wavelet", default="db9")
+    p.add_argument("--threshold", type=float, default=None)
+    p.add_argument("--crossover", type=float, default=10)
+    p.add_argument("--padding_mode", default="reflect")
+    p.add_argument("--bidirectional", action="store_true")
+    p.add_argument("--workers", type=int, default=None, help="accepted and ignored")
+    p.add_argument("--chunks", type=int, default=1, help="accepted and ignored")
+    p.add_argument("--compression_method", default="ADOBE_DEFLATE")
+    p.add_argument("--compression_level", type=int, default=1)
+    p.add_argument("--flat", default=None, help="flat-field reference image (TIFF)")
+    p.add_argument("--dark", type=float, default=0)
+    p.add_argument("--zstep", type=float, default=None, help="accepted and ignored (.dcimg only)")
+    p.add_argument("--rotate", type=int, default=0)
+    p.add_argument("--flip_upside_down", action="store_true")
+    p.add_argument("--lightsheet", action="store_true")
+    p.add_argument("--down_sample", type=int, nargs=2, default=None, metavar=("DY", "DX"))
+    p.add_argument("--down_sample_method", default="max")
+    p.add_argument("--convert_to_16bit", action="store_true")
+    p.add_argument("--convert_to_8bit", action="store_true")
+    p.add_argument("--bit_shift_to_right", type=int, default=8)
+    p.add_argument("--continue_process", action="store_true")
+    p.add_argument("--dtype", default=None)
+    p.add_argument("--tile_size", type=int, nargs=2, default=None, metavar=("NY", "NX"))
+    p.add_argument("--gaussian_filter_2d", action="store_true", help="accepted; does nothing, as in the reference")
+    p.add_argument("--max_batch", type=int, default=None, help="tiles per launch (default: from the free device memory)")
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    a = _parse_args(argv)
+    inp = Path(a.input)
+    out = Path(a.output) if a.output else inp.parent / (inp.name + "_destriped")
+    flat = None
+    if a.flat:
+        flat = imread_tif_raw_png(Path(a.flat))
+        if flat is None:
+            raise SystemExit(f"--flat={a.flat}: cannot be read")
+    stats = {}
+    rc = batch_filter(inp, out, flat=flat, gaussian_filter_2d=a.gaussian_filter_2d, sigma=(a.sigma1, a.sigma2), level=a.level,
+                      wavelet=a.wavelet, crossover=a.crossover, threshold=a.threshold, padding_mode=a.padding_mode,
+                      bidirectional=a.bidirectional, dark=a.dark, rotate=a.rotate, flip_upside_down=a.flip_upside_down,
+                      lightsheet=a.lightsheet, convert_to_16bit=a.convert_to_16bit, convert_to_8bit=a.convert_to_8bit,
+                      bit_shift_to_right=a.bit_shift_to_right, continue_process=a.continue_process, d_type=a.dtype,
+                      tile_size=tuple(a.tile_size) if a.tile_size else None, down_sample=tuple(a.down_sample) if a.down_sample else None,
+                      down_sample_method=a.down_sample_method, compression=(a.compression_method, a.compression_level),
+                      max_batch=a.max_batch, stats=stats)
+    print("pystripe: {files} files, {written} written, {skipped_existing} already there, {skipped_unreadable} unreadable, "
+          "{zero_tiles} zero tiles; read {read_s:.2f} s, compute {compute_s:.2f} s, write {write_s:.2f} s".format(**stats))
+    return rc
+
+
+if __name__ == "__main__":
+    sys.exit(main())

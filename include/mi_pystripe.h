@@ -1,0 +1,80 @@
+/* mi_pystripe.h -- pystripe tile preprocessing: the wavelet-FFT stripe filter and the per-tile conversions around it, on
+ * batches of equally shaped 2-D tiles in device memory.
+ *
+ * Replaces, for the options process_images.py uses, pystripe/core.py:
+ *   process_img            :1190-1381  (uniform tile, flat, down_sample, filter_streaks, dark, 8/16-bit conversion, flip, rotate)
+ *   filter_streaks         :982-1159   (log1p, padding, filter_streak_dual_band, crop, expm1, rint + clip for integer tiles)
+ *   filter_streak_dual_band:943-979    (sigma1 == sigma2: one filter_subband; else one after the other)
+ *   filter_subband         :927-940    (numpy branch: wavedec2 'symmetric' db9, np_filter_coefficient on cH and cV, waverec2)
+ *   np_filter_coefficient  :749-754, np_notch :637-667  (gains applied by PACKED position of scipy.fftpack.rfft's real spectrum)
+ *   calculate_pad_size     :681-698, notch_rise_point :670-678, convert_to_8bit_fun :402-425, convert_to_16bit_fun :397-399,
+ *   is_uniform_2d          :107-121,  calculate_down_sampled_size :1162-1170
+ * skimage.measure.block_reduce (zero padding to a multiple of the block) is restated for max / min / mean.
+ *
+ * Not built (refused by the Python layer by name): bleach correction, masking, lightsheet, dark-edge exclusion, new_size,
+ * wavelets other than db9, padding modes other than reflect / wrap / symmetric / edge, the median down-sampling.
+ */
+#ifndef MI_PYSTRIPE_H
+#define MI_PYSTRIPE_H
+
+#include "mi_common.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef enum { MI_PS_U8 = 0, MI_PS_U16 = 1, MI_PS_F32 = 2 } mi_pystripe_dtype;
+typedef enum { MI_PS_REFLECT = 0, MI_PS_WRAP = 1, MI_PS_SYMMETRIC = 2, MI_PS_EDGE = 3 } mi_pystripe_padding;   /* numpy.pad modes */
+typedef enum { MI_PS_DOWN_MAX = 0, MI_PS_DOWN_MIN = 1, MI_PS_DOWN_MEAN = 2 } mi_pystripe_down;
+#define MI_PS_MAX_LEVELS 24
+
+typedef struct {
+    double sigma1, sigma2;     /* (0, 0): no stripe filter; both > 0 otherwise ("sigma must be positive", np_notch :654) */
+    int level;                 /* 0: min over both padded extents of floor(log2(n / 17)) */
+    int padding_mode;          /* mi_pystripe_padding */
+    int bidirectional;         /* also filter cV along axis -2 */
+    int down_y, down_x;        /* block of down_sample (1: that axis is kept); both 0: no down_sample at all */
+    int down_method;           /* mi_pystripe_down */
+    int use_flat;              /* divide by the flat field given to mi_pystripe_run (float32; the tile turns into a float tile) */
+    float dark;                /* > 0: where(img > dark, img - dark, 0) in the tile's own kind (truncated for integer tiles) */
+    int convert_to_16bit;      /* clip 0..65535, truncate */
+    int convert_to_8bit;       /* convert_to_8bit_fun with bit_shift (0..8) */
+    int bit_shift;
+    int out_dtype;             /* mi_pystripe_dtype of the result (d_type; uint16 / uint8 when a conversion flag is set) */
+    int flip_upside_down;
+    int rotate;                /* 0, 90, 180, 270: numpy.rot90(img, rotate / 90) after the flip */
+    int log_output;            /* 1: float32 output of the filtered image BEFORE expm1 (cropped, nothing after it applied) */
+    int max_batch;             /* tiles that go through one launch (scratch is held for this many); <= 0: 16 */
+    int keep_uniform;          /* 1: no uniform-tile rule (filter_streaks called on its own filters a uniform tile like any other) */
+} mi_pystripe_params;
+
+typedef struct {
+    int ny, nx;                /* tile after down_sample */
+    int base_pad, pad_y, pad_x;/* calculate_pad_size and the extra rows / columns at the end (odd extent, 34-pixel rule) */
+    int padded_ny, padded_nx;
+    int levels;
+    int coef_ny[MI_PS_MAX_LEVELS], coef_nx[MI_PS_MAX_LEVELS];   /* detail shapes, finest level first */
+    int out_ny, out_nx, out_dtype;
+    int integer_kind;          /* 1: the tile is an integer tile inside process_img (rint + clip after expm1, truncating dark) */
+    int max_batch;
+    size_t scratch_bytes_per_tile;
+} mi_pystripe_info;
+
+/* A plan for tiles of ny x nx samples of in_dtype on device dev.  Synchronises (uploads its tables).  A plan owns its scratch:
+ * one thread and one stream use it at a time. */
+int mi_pystripe_plan_create(int dev, int ny, int nx, int in_dtype, const mi_pystripe_params* params, void** plan);
+int mi_pystripe_plan_destroy(void* plan);
+int mi_pystripe_plan_info(void* plan, mi_pystripe_info* info);
+/* The bookkeeping alone, without a device: what a plan for this shape would derive (scratch_bytes_per_tile included). */
+int mi_pystripe_derive(int ny, int nx, int in_dtype, const mi_pystripe_params* params, mi_pystripe_info* info);
+/* count tiles, dense one after the other in `in` (ny x nx of in_dtype) -> `out` (out_ny x out_nx of out_dtype); flat: ny x nx
+ * float32 on the device when params.use_flat, else NULL.  Tiles are independent: a tile's result does not depend on count or
+ * on its place in the batch.  Enqueues on `stream`; the first call (and a call after a larger count) allocates the scratch. */
+int mi_pystripe_run(void* plan, void* stream, const void* in, const void* flat, void* out, int64_t count);
+/* calculate_pad_size(shape=(ny, nx), sigma) (:681) */
+int mi_pystripe_pad_size(int ny, int nx, double sigma);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* MI_PYSTRIPE_H */
