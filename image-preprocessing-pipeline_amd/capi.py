@@ -76,6 +76,21 @@ class PystripeInfo(C.Structure):
                 ("integer_kind", C.c_int), ("max_batch", C.c_int), ("scratch_bytes_per_tile", C.c_size_t)]
 
 
+class LightsheetParams(C.Structure):
+    """mi_lightsheet_params (include/mi_lightsheet.h)."""
+    _fields_ = [("artifact_length", C.c_int), ("artifact_along_y", C.c_int), ("background_window_size", C.c_int), ("background_spacing", C.c_int),
+                ("background_step", C.c_int), ("percentile", C.c_double), ("lightsheet_vs_background", C.c_double),
+                ("factor_is_integer", C.c_int), ("map_dtype", C.c_int), ("max_batch", C.c_int)]
+
+
+class LightsheetInfo(C.Structure):
+    """mi_lightsheet_info (include/mi_lightsheet.h)."""
+    _fields_ = [(name, C.c_int) for name in (
+        "ny", "nx", "ls_ny", "ls_nx", "ls_left_y", "ls_left_x", "bg_ny", "bg_nx", "bg_left_y", "bg_left_x", "bg_first_y0", "bg_first_y1", "bg_last_y0",
+        "bg_last_y1", "bg_first_x0", "bg_first_x1", "bg_last_x0", "bg_last_x1", "max_window_samples", "ls_zero_last_row", "ls_zero_last_col",
+        "bg_zero_last_row", "bg_zero_last_col", "integer_mode", "max_batch")] + [("scratch_bytes_per_tile", C.c_size_t)]
+
+
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _ip = C.POINTER(C.c_int)
 
@@ -172,6 +187,13 @@ SIGNATURES = {
     "mi_pystripe_derive": (_i, [_i, _i, _i, C.POINTER(PystripeParams), C.POINTER(PystripeInfo)]),
     "mi_pystripe_run": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64]),
     "mi_pystripe_pad_size": (_i, [_i, _i, C.c_double]),
+    # mi_lightsheet.h
+    "mi_lightsheet_derive": (_i, [_i, _i, _i, C.POINTER(LightsheetParams), C.POINTER(LightsheetInfo)]),
+    "mi_lightsheet_plan_create": (_i, [_i, _i, _i, _i, C.POINTER(LightsheetParams), C.POINTER(_vp)]),
+    "mi_lightsheet_plan_destroy": (_i, [_vp]),
+    "mi_lightsheet_plan_info": (_i, [_vp, C.POINTER(LightsheetInfo)]),
+    "mi_lightsheet_run": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64]),
+    "mi_lightsheet_local_percentile": (_i, [_i, _vp, _vp, _i, _i, _i, C.c_int64] + [_i] * 6 + [C.c_double, _i, _vp, _i]),
     # mi_crossmips.h
     "mi_ncc_default_params": (None, [_i, _i, _i, C.POINTER(NccParams)]),
     "mi_ncc_mips": (_i, [_i, _vp, _vp, _vp] + [_i] * 10 + [C.POINTER(NccParams), C.POINTER(NccDescr)]),

@@ -13,17 +13,20 @@ an error.
 What is computed (reference line numbers in include/mi_pystripe.h): uniform tile -> zeros; flat field; ``down_sample`` (max / min /
 mean, zero-padded blocks like skimage's ``block_reduce``); ``filter_streaks`` = log1p, numpy padding (reflect / wrap / symmetric /
 edge), db9 wavelet decomposition, the packed-position Gaussian notch on cH (and cV when ``bidirectional``), reconstruction, crop,
-expm1, rint + clip for integer tiles; ``dark``; 8 / 16-bit conversion; flip; rotation.
+expm1, rint + clip for integer tiles; ``dark``; ``lightsheet`` (pystripe/lightsheet_correct.py: local percentiles on two sub-grids,
+order-1 resampling, subtraction; include/mi_lightsheet.h); 8 / 16-bit conversion; flip; rotation.
 
 Departures, all stated in INTEGRATION.md:
   * ``flat`` on an integer tile: the reference's in-place divide raises; here the tile is divided in float32 and is a float tile from
     there on (the float32-tile case matches the reference);
   * ``gaussian_filter_2d`` is accepted and does nothing, as in the reference (its GaussianBlur result is discarded);
-  * refused by name: ``bleach_correction_frequency``, ``enable_masking``, ``lightsheet``, ``exclude_dark_edges_set_them_to_zero``,
+  * ``lightsheet=True`` on a tile narrower than ``artifact_length`` or with an extent below 25 is refused (the reference returns
+    zeros for a uniform such tile and divides by zero otherwise);
+  * refused by name: ``bleach_correction_frequency``, ``enable_masking``, ``exclude_dark_edges_set_them_to_zero``,
     ``new_size``, ``.dcimg`` input, ``down_sample_method='median'``, wavelets other than ``db9``, other padding modes, a ``threshold``
     (``use_thresholding`` is never set on this path; ``crossover`` has no effect there either);
   * accepted and ignored: ``workers``, ``threads_per_gpu``, ``timeout``, ``gpu_semaphore``, ``z_step``, ``print_input_file_names``,
-    ``verbose`` and the lightsheet tuning numbers.
+    ``verbose``.
 The command line takes the reference's LONG option names with plain ``store_true`` flags; the reference's own parser cannot be built
 (``-w`` is given to two options), so the CLI is not claimed as a byte-for-byte drop-in.
 """
@@ -111,7 +114,7 @@ def _check_unsupported(kw):
     """Raises NotImplementedError naming the first option this build does not do."""
     if kw.get("bleach_correction_frequency") is not None:
         _refuse("bleach_correction_frequency", kw["bleach_correction_frequency"], "bleach correction is not built")
-    for name in ("enable_masking", "lightsheet", "exclude_dark_edges_set_them_to_zero"):
+    for name in ("enable_masking", "exclude_dark_edges_set_them_to_zero"):
         if kw.get(name):
             _refuse(name, kw[name], "not built (needs OpenCV / scikit-image semantics)")
     if kw.get("new_size") is not None:
@@ -246,8 +249,8 @@ class Plan:
             pass
 
 
-def _run_tiles(img, flat, device, **opts):
-    """img: 2-D tile or [n, ny, nx] stack, numpy or device tensor -> the same kind of container."""
+def _as_stack(img, device):
+    """img: 2-D tile or [n, ny, nx] stack, numpy or device tensor -> (contiguous device stack, single, is_tensor, numpy dtype)"""
     import torch
     is_tensor = isinstance(img, torch.Tensor)
     if is_tensor:
@@ -262,7 +265,249 @@ def _run_tiles(img, flat, device, **opts):
     single = tiles.dim() == 2
     if tiles.dim() not in (2, 3):
         raise ValueError(f"a 2-D tile or a stack [n, ny, nx] is expected, got shape {tuple(tiles.shape)}")
-    tiles = (tiles[None] if single else tiles).contiguous()
+    return (tiles[None] if single else tiles).contiguous(), single, is_tensor, in_dtype
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# lightsheet correction (pystripe/lightsheet_correct.py; include/mi_lightsheet.h)
+
+BACKGROUND_SPACING, BACKGROUND_STEP = 25, 2   # process_img's choice (pystripe/core.py:1343-1346)
+
+
+def check_lightsheet_shape(shape, artifact_length=150, spacing=BACKGROUND_SPACING):
+    """Raises NotImplementedError when a tile of ``shape`` holds no window centre: the reference then divides by zero in zoom (or
+    returns zeros when the tile is uniform); this build refuses it from the shape alone."""
+    ny, nx = int(shape[-2]), int(shape[-1])
+    if nx < artifact_length or ny < spacing or nx < spacing:
+        raise NotImplementedError(f"lightsheet=True: a tile of shape {(ny, nx)} is narrower than artifact_length={artifact_length} or has "
+                                  f"an extent below the background spacing {spacing}: no window centre fits (the reference fails here too)")
+
+
+def make_lightsheet_params(map_dtype, artifact_length=150, background_window_size=200, percentile=0.25, lightsheet_vs_background=2.0,
+                           spacing=BACKGROUND_SPACING, step=BACKGROUND_STEP, along_y=False, max_batch=0):
+    """mi_lightsheet_params for process_img's lightsheet options."""
+    if isinstance(percentile, (tuple, list, np.ndarray)):
+        _refuse("percentile", percentile, "one percentile is built, not a list")
+    if not 0 <= float(percentile) <= 1:
+        raise ValueError(f"Percentiles must be in the range [0, 100] (percentile={percentile!r} stands for {100 * percentile})")
+    p = capi.LightsheetParams()
+    p.artifact_length, p.artifact_along_y = int(artifact_length), int(bool(along_y))
+    p.background_window_size, p.background_spacing, p.background_step = int(background_window_size), int(spacing), int(step)
+    p.percentile, p.lightsheet_vs_background = float(percentile), float(lightsheet_vs_background)
+    p.factor_is_integer = int(isinstance(lightsheet_vs_background, (int, np.integer)) and not isinstance(lightsheet_vs_background, bool))
+    p.map_dtype, p.max_batch = _dtype_code(map_dtype, "d_type"), int(max_batch)
+    return p
+
+
+def derive_lightsheet(shape, in_dtype, params):
+    """The bookkeeping of a lightsheet plan without a device (centres, window bounds, largest window, zero lines, scratch)."""
+    info = capi.LightsheetInfo()
+    capi.check(capi.lib().mi_lightsheet_derive(int(shape[0]), int(shape[1]), _dtype_code(in_dtype, "dtype"), C.byref(params), C.byref(info)))
+    return info
+
+
+class LightsheetPlan:
+    """mi_lightsheet plan for tiles of one shape and dtype.  ``run(tiles)`` corrects a [n, ny, nx] device tensor (in place unless
+    ``out`` is given) and returns (out, lightsheet maps or None, background maps or None)."""
+
+    def __init__(self, device, shape, in_dtype, params):
+        import torch
+        capi.require_gpu()
+        self.device = torch.device(device if device is not None else "cuda:0")
+        self.shape, self.in_dtype, self.params = (int(shape[0]), int(shape[1])), np.dtype(in_dtype), params
+        self.map_dtype = _CODE_NP[params.map_dtype]
+        self._h = C.c_void_p()
+        capi.check(capi.lib().mi_lightsheet_plan_create(self.device.index or 0, self.shape[0], self.shape[1], _dtype_code(in_dtype, "dtype"),
+                                                        C.byref(params), C.byref(self._h)))
+        self.info = capi.LightsheetInfo()
+        capi.check(capi.lib().mi_lightsheet_plan_info(self._h, C.byref(self.info)))
+
+    def run(self, tiles, out=None, return_lightsheet=False, return_background=False):
+        import torch
+        tdt = getattr(torch, self.in_dtype.name)
+        if not (isinstance(tiles, torch.Tensor) and tiles.is_cuda and tiles.is_contiguous() and tiles.dim() == 3 and tiles.dtype == tdt
+                and tuple(tiles.shape[1:]) == self.shape):
+            raise ValueError(f"LightsheetPlan.run: a contiguous [n, {self.shape[0]}, {self.shape[1]}] {self.in_dtype.name} device tensor "
+                             "is expected")
+        out = tiles if out is None else out
+        if out.shape != tiles.shape or out.dtype != tiles.dtype or not out.is_contiguous():
+            raise ValueError("LightsheetPlan.run: out must look like the input")
+        mdt = getattr(torch, self.map_dtype.name)
+        ls = torch.empty(tiles.shape, dtype=mdt, device=tiles.device) if return_lightsheet else None
+        bg = torch.empty(tiles.shape, dtype=mdt, device=tiles.device) if return_background else None
+        with torch.cuda.device(tiles.device):
+            capi.check(capi.lib().mi_lightsheet_run(self._h, capi.current_stream_ptr(tiles.device), tiles.data_ptr(), out.data_ptr(),
+                                                    None if ls is None else ls.data_ptr(), None if bg is None else bg.data_ptr(),
+                                                    int(tiles.shape[0])))
+        return out, ls, bg
+
+    def close(self):
+        if self._h:
+            capi.lib().mi_lightsheet_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _pair(value, name, default=None):
+    """(y, x) of a 2- or 3-tuple of the reference (its images carry a third axis of one sample)."""
+    if value is None:
+        return default
+    if isinstance(value, np.ndarray):
+        _refuse(name, "array", "only rectangular windows given as a tuple are built")
+    v = tuple(1 if e is None else int(e) for e in value)
+    if len(v) == 3 and v[2] == 1:
+        v = v[:2]
+    if len(v) != 2:
+        raise ValueError(f"Dimension mismatch in the parameters! ({name}={value!r} for a 2-D image)")
+    return v
+
+
+def local_percentile(source, percentile, selem=(50, 50), spacing=None, step=None, interpolate=1, mask=None, dtype=None, device=None):
+    """pystripe/lightsheet_correct.py:245 on the GPU for one percentile and a rectangular window: the local percentiles on the
+    sub-grid (``interpolate=None``) or resampled to the image shape (``interpolate=1``).  ``source``: a 2-D image or a stack
+    [n, ny, nx], numpy or device tensor.  Tuples may carry the reference's third entry of 1."""
+    import torch
+    if mask is not None:
+        _refuse("mask", "array", "masked windows are not built")
+    if isinstance(percentile, (tuple, list, np.ndarray)):
+        _refuse("percentile", percentile, "one percentile is built, not a list")
+    if interpolate not in (None, 0, 1) or interpolate is False:
+        _refuse("interpolate", interpolate, "order 1 and None (the sub-grid) are built")
+    if not 0 <= float(percentile) <= 1:
+        raise ValueError(f"Percentiles must be in the range [0, 100] (percentile={percentile!r} stands for {100 * percentile})")
+    selem = _pair(selem, "selem")
+    spacing = _pair(spacing, "spacing", selem)
+    step = _pair(step, "step", (1, 1))
+    tiles, single, is_tensor, in_dtype = _as_stack(source, device)
+    n, ny, nx = (int(v) for v in tiles.shape)
+    out_dtype = np.dtype(in_dtype if dtype is None else dtype)
+    if ny < spacing[0] or nx < spacing[1]:
+        raise NotImplementedError(f"local_percentile: an image of shape {(ny, nx)} holds no centre at spacing={spacing}")
+    shape = (n, ny, nx) if interpolate else (n, ny // spacing[0], nx // spacing[1])
+    out = torch.empty(shape, dtype=getattr(torch, out_dtype.name), device=tiles.device)
+    with torch.cuda.device(tiles.device):
+        capi.check(capi.lib().mi_lightsheet_local_percentile(
+            tiles.device.index or 0, capi.current_stream_ptr(tiles.device), tiles.data_ptr(), _dtype_code(in_dtype, "source.dtype"), ny, nx, n,
+            selem[0], selem[1], spacing[0], spacing[1], step[0], step[1], float(percentile), int(bool(interpolate)), out.data_ptr(),
+            _dtype_code(out_dtype, "dtype")))
+    out = out[0] if single else out
+    return out if is_tensor else out.cpu().numpy()
+
+
+def correct_lightsheet(img, percentile=0.25, mask=None, lightsheet=dict(selem=(150, 1, 1)),
+                       background=dict(selem=(200, 200, 1), spacing=(25, 25, 1), interpolate=1, dtype=None, step=(2, 2, 1)),
+                       lightsheet_vs_background=2.0, return_lightsheet=False, return_background=False, device=None):
+    """pystripe/lightsheet_correct.py:31 on the GPU: ``img - min(img, min(ls, bg * lightsheet_vs_background))`` with ``ls`` the local
+    percentile in a window along the lightsheet and ``bg`` the one in a square window, both resampled to the image.  ``img``: a 2-D
+    tile or a stack [n, ny, nx], numpy or device tensor; the result is new (the reference works in place).  Built: a ``lightsheet``
+    window (1, L) or (L, 1) at its own spacing, a square ``background`` window with one spacing and one step, ``interpolate=1``."""
+    import torch
+    if mask is not None:
+        _refuse("mask", "array", "masked windows are not built")
+    ls_kw = dict(dict(selem=(50, 50), spacing=None, step=None, interpolate=1, mask=None, dtype=None), **lightsheet)
+    bg_kw = dict(dict(selem=(50, 50), spacing=None, step=None, interpolate=1, mask=None, dtype=None), **background)
+    for name, kw in (("lightsheet", ls_kw), ("background", bg_kw)):
+        if kw["mask"] is not None:
+            _refuse(f"{name}['mask']", "array", "masked windows are not built")
+        if kw["interpolate"] != 1:
+            _refuse(f"{name}['interpolate']", kw["interpolate"], "order 1 is built")
+    ls_sel, bg_sel = _pair(ls_kw["selem"], "lightsheet['selem']"), _pair(bg_kw["selem"], "background['selem']")
+    ls_space, bg_space = _pair(ls_kw["spacing"], "lightsheet['spacing']", ls_sel), _pair(bg_kw["spacing"], "background['spacing']", bg_sel)
+    ls_step, bg_step = _pair(ls_kw["step"], "lightsheet['step']", (1, 1)), _pair(bg_kw["step"], "background['step']", (1, 1))
+    if min(ls_sel) != 1 or ls_space != ls_sel or ls_step != (1, 1):
+        _refuse("lightsheet", lightsheet, "a window (1, L) or (L, 1) at its own spacing without a step is built")
+    if bg_sel[0] != bg_sel[1] or bg_space[0] != bg_space[1] or bg_step[0] != bg_step[1]:
+        _refuse("background", background, "a square window with one spacing and one step is built")
+    tiles, single, is_tensor, in_dtype = _as_stack(img, device)
+    map_dtype = np.dtype(in_dtype if ls_kw["dtype"] is None else ls_kw["dtype"])
+    if np.dtype(in_dtype if bg_kw["dtype"] is None else bg_kw["dtype"]) != map_dtype:
+        _refuse("background['dtype']", bg_kw["dtype"], "one dtype for both estimates is built")
+    along_y = ls_sel[1] == 1 and ls_sel[0] != 1
+    length = max(ls_sel)
+    ny, nx = (int(v) for v in tiles.shape[1:])
+    if (ny if along_y else nx) < length or ny < bg_space[0] or nx < bg_space[0]:
+        raise NotImplementedError(f"lightsheet: a tile of shape {(ny, nx)} holds no window centre for selem={ls_sel}, spacing={bg_space}")
+    prm = make_lightsheet_params(map_dtype, length, bg_sel[0], percentile, lightsheet_vs_background, bg_space[0], bg_step[0], along_y,
+                                 max_batch=min(int(tiles.shape[0]), 16))
+    plan = LightsheetPlan(tiles.device, (ny, nx), in_dtype, prm)
+    try:
+        got = plan.run(tiles, torch.empty_like(tiles), return_lightsheet, return_background)
+        torch.cuda.synchronize(tiles.device)
+    finally:
+        plan.close()
+    got = [g if is_tensor else g.cpu().numpy() for g in ((a[0] if single else a) for a in got if a is not None)]
+    return got[0] if len(got) == 1 else tuple(got)
+
+
+class Pipeline:
+    """process_img for tiles of one shape and dtype: one pystripe plan, or -- with ``lightsheet`` (a dict of artifact_length,
+    background_window_size, percentile, lightsheet_vs_background) -- three steps that stay on the device: the pystripe plan up to and
+    including ``dark`` in the tile's own kind, the lightsheet plan in place, and a filter-less pystripe plan for conversion, flip
+    and rotation (left out when it would change nothing)."""
+
+    def __init__(self, device, shape, in_dtype, flat=False, lightsheet=None, max_batch=0, **opts):
+        in_dtype = np.dtype(in_dtype)
+        self.tail = self.ls = None
+        if lightsheet is None:
+            self.head = Plan(device, shape, in_dtype, make_params(in_dtype, flat=flat, max_batch=max_batch, **opts))
+            return
+        tail_names = ("rotate", "flip_upside_down", "convert_to_16bit", "convert_to_8bit", "bit_shift_to_right")
+        entry_type = np.dtype(in_dtype if opts.get("d_type") is None else opts["d_type"])
+        head_opts = {k: v for k, v in opts.items() if k not in tail_names}
+        prm = make_params(in_dtype, flat=flat, max_batch=max_batch, **dict(head_opts, d_type=in_dtype))
+        info = derive(shape, in_dtype, prm)
+        mid_type = in_dtype if info.integer_kind else np.dtype(np.float32)   # the kind the tile has after ``dark``
+        prm.out_dtype = _dtype_code(mid_type, "dtype")
+        mid_shape = (info.ny, info.nx)
+        check_lightsheet_shape(mid_shape, lightsheet.get("artifact_length", 150))
+        ls_prm = make_lightsheet_params(entry_type, max_batch=max_batch, **lightsheet)
+        tail_prm = make_params(mid_type, max_batch=max_batch, keep_uniform=True, d_type=entry_type, **{k: opts[k] for k in tail_names if k in opts})
+        tail_info = derive(mid_shape, mid_type, tail_prm)
+        self.head = Plan(device, shape, in_dtype, prm)
+        try:
+            self.ls = LightsheetPlan(device, mid_shape, mid_type, ls_prm)
+            changes = tail_prm.rotate or tail_prm.flip_upside_down or _CODE_NP[tail_info.out_dtype] != mid_type
+            if changes:
+                self.tail = Plan(device, mid_shape, mid_type, tail_prm)
+        except Exception:
+            self.close()
+            raise
+
+    def run(self, tiles, flat=None):
+        out = self.head.run(tiles, flat)
+        if self.ls is not None:
+            self.ls.run(out)
+        if self.tail is not None:
+            out = self.tail.run(out)
+        return out
+
+    def close(self):
+        for plan in (self.head, self.ls, self.tail):
+            if plan is not None:
+                plan.close()
+
+
+def _lightsheet_opts(lightsheet, shape, down_sample, artifact_length, background_window_size, percentile, lightsheet_vs_background):
+    """None, or the options of the lightsheet step after the shape check that needs no device."""
+    if not lightsheet:
+        return None
+    shape = tuple(int(v) for v in shape[-2:])
+    if down_sample is not None:
+        shape = calculate_down_sampled_size(shape, down_sample)
+    check_lightsheet_shape(shape, artifact_length)
+    return dict(artifact_length=artifact_length, background_window_size=background_window_size, percentile=percentile,
+                lightsheet_vs_background=lightsheet_vs_background)
+
+
+def _run_tiles(img, flat, device, lightsheet=None, **opts):
+    """img: 2-D tile or [n, ny, nx] stack, numpy or device tensor -> the same kind of container."""
+    import torch
+    tiles, single, is_tensor, in_dtype = _as_stack(img, device)
     shape = tuple(int(v) for v in tiles.shape[1:])
     flat_t = None
     if flat is not None:
@@ -271,8 +516,7 @@ def _run_tiles(img, flat, device, **opts):
             flat_t = flat_t.to(tiles.device, torch.float32).contiguous()
         else:
             warnings.warn("warning: image and flat arrays had different shapes")
-    params = make_params(in_dtype, flat=flat_t is not None, max_batch=min(int(tiles.shape[0]), 16), **opts)
-    plan = Plan(tiles.device, shape, in_dtype, params)
+    plan = Pipeline(tiles.device, shape, in_dtype, flat=flat_t is not None, lightsheet=lightsheet, max_batch=min(int(tiles.shape[0]), 16), **opts)
     try:
         out = plan.run(tiles, flat_t)
         torch.cuda.synchronize(tiles.device)
@@ -307,11 +551,13 @@ def process_img(img, flat=None, gaussian_filter_2d=False, down_sample=None, down
                 convert_to_16bit=False, convert_to_8bit=False, bit_shift_to_right=8, d_type=None, verbose=False, device=None):
     """pystripe/core.py:1190 on the GPU, the reference's keywords and defaults (so ``wavelet`` must be given as 'db9' when ``sigma`` asks
     for the filter).  ``gaussian_filter_2d`` does nothing, as in the reference, whose GaussianBlur result is discarded.  ``img`` may be
-    a stack [n, ny, nx] of equally shaped tiles (an addition): they go through every launch together."""
-    _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, lightsheet=lightsheet, new_size=new_size,
+    a stack [n, ny, nx] of equally shaped tiles (an addition): they go through every launch together.  ``lightsheet=True`` runs
+    ``correct_lightsheet`` after ``dark`` as the reference does; a tile too small for one window is refused from its shape alone."""
+    _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, new_size=new_size,
                             exclude_dark_edges_set_them_to_zero=exclude_dark_edges_set_them_to_zero, threshold=threshold,
                             log1p_normalization_needed=log1p_normalization_needed))
-    return _run_tiles(img, flat, device, down_sample=down_sample, down_sample_method=down_sample_method, sigma=sigma, level=level,
+    ls = _lightsheet_opts(lightsheet, img.shape, down_sample, artifact_length, background_window_size, percentile, lightsheet_vs_background)
+    return _run_tiles(img, flat, device, lightsheet=ls, down_sample=down_sample, down_sample_method=down_sample_method, sigma=sigma, level=level,
                       wavelet=wavelet, padding_mode=padding_mode, bidirectional=bidirectional, dark=dark, rotate=rotate,
                       flip_upside_down=flip_upside_down, convert_to_16bit=convert_to_16bit, convert_to_8bit=convert_to_8bit,
                       bit_shift_to_right=bit_shift_to_right, d_type=d_type)
@@ -420,8 +666,7 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
     import torch
     if convert_to_16bit and convert_to_8bit:
         raise TypeError("convert_to_16bit and convert_to_8bit are both set: choose one output format")
-    _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, lightsheet=lightsheet, new_size=new_size,
-                            threshold=threshold))
+    _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, new_size=new_size, threshold=threshold))
     input_path, output_path = Path(input_path), Path(output_path)
     if input_path.suffix.lower() == ".dcimg":
         _refuse("input_path", str(input_path), ".dcimg input is not built")
@@ -521,8 +766,10 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
                 print("warning: image and flat arrays had different shapes")
             key = (shape, dt, use_flat)
             if key not in plans:
-                prm = make_params(dt, flat=use_flat, max_batch=chunk, **opts)
-                plans[key] = (Plan(device, shape, dt, prm), torch.from_numpy(flat).to(device) if use_flat else None)
+                ls = _lightsheet_opts(lightsheet, shape, down_sample, artifact_length, background_window_size, percentile,
+                                      lightsheet_vs_background)
+                plans[key] = (Pipeline(device, shape, dt, flat=use_flat, lightsheet=ls, max_batch=chunk, **opts),
+                              torch.from_numpy(flat).to(device) if use_flat else None)
             plan, flat_t = plans[key]
             stack = torch.from_numpy(np.stack([m[0] for m in members])).to(device)
             out = plan.run(stack, flat_t).cpu().numpy()
@@ -588,7 +835,11 @@ def _parse_args(argv=None):
     p.add_argument("--zstep", type=float, default=None, help="accepted and ignored (.dcimg only)")
     p.add_argument("--rotate", type=int, default=0)
     p.add_argument("--flip_upside_down", action="store_true")
-    p.add_argument("--lightsheet", action="store_true")
+    p.add_argument("--lightsheet", action="store_true", help="lightsheet correction (background subtraction) after --dark")
+    p.add_argument("--artifact_length", type=int, default=150, help="length of the lightsheet window along x [pixels]")
+    p.add_argument("--background_window_size", type=int, default=200, help="side of the background window [pixels]")
+    p.add_argument("--percentile", type=float, default=0.25, help="percentile of both estimates, in [0, 1]")
+    p.add_argument("--lightsheet_vs_background", type=float, default=2.0, help="factor on the background estimate")
     p.add_argument("--down_sample", type=int, nargs=2, default=None, metavar=("DY", "DX"))
     p.add_argument("--down_sample_method", default="max")
     p.add_argument("--convert_to_16bit", action="store_true")
@@ -615,7 +866,8 @@ def main(argv=None):
     rc = batch_filter(inp, out, flat=flat, gaussian_filter_2d=a.gaussian_filter_2d, sigma=(a.sigma1, a.sigma2), level=a.level,
                       wavelet=a.wavelet, crossover=a.crossover, threshold=a.threshold, padding_mode=a.padding_mode,
                       bidirectional=a.bidirectional, dark=a.dark, rotate=a.rotate, flip_upside_down=a.flip_upside_down,
-                      lightsheet=a.lightsheet, convert_to_16bit=a.convert_to_16bit, convert_to_8bit=a.convert_to_8bit,
+                      lightsheet=a.lightsheet, artifact_length=a.artifact_length, background_window_size=a.background_window_size,
+                      percentile=a.percentile, lightsheet_vs_background=a.lightsheet_vs_background, convert_to_16bit=a.convert_to_16bit, convert_to_8bit=a.convert_to_8bit,
                       bit_shift_to_right=a.bit_shift_to_right, continue_process=a.continue_process, d_type=a.dtype,
                       tile_size=tuple(a.tile_size) if a.tile_size else None, down_sample=tuple(a.down_sample) if a.down_sample else None,
                       down_sample_method=a.down_sample_method, compression=(a.compression_method, a.compression_level),

@@ -11,8 +11,9 @@
  *   is_uniform_2d          :107-121,  calculate_down_sampled_size :1162-1170
  * skimage.measure.block_reduce (zero padding to a multiple of the block) is restated for max / min / mean.
  *
- * Not built (refused by the Python layer by name): bleach correction, masking, lightsheet, dark-edge exclusion, new_size,
- * wavelets other than db9, padding modes other than reflect / wrap / symmetric / edge, the median down-sampling.
+ * Not built (refused by the Python layer by name): bleach correction, masking, dark-edge exclusion, new_size, wavelets other than
+ * db9, padding modes other than reflect / wrap / symmetric / edge, the median down-sampling.  The lightsheet correction of
+ * process_img :1333-1348 is mi_lightsheet.h; the Python layer runs it between two plans of this header.
  */
 #ifndef MI_PYSTRIPE_H
 #define MI_PYSTRIPE_H
