@@ -12,7 +12,7 @@ struct NativeDims {
     int ly2, r3;
     int lz2, r3z;
     int hx, ny, nz;
-    int ty, tc, tl;   // rows per x tile, columns per y tile, lines per z tile (A and B tiles each)
+    int ty, tc, tl;  // rows per x tile, columns per y tile, lines per z tile (A and B tiles each)
     // padded grids: planes z >= z_in_hi of a convolution's input are all zero (never stored, never loaded); of its result only
     // planes [z_out_lo, z_out_hi) and rows < y_out_hi are ever read.  Whole grid when nothing is padded.
     int z_in_hi, z_out_lo, z_out_hi, y_out_hi;
@@ -22,6 +22,10 @@ struct NativeDims {
     int xrow;         // x side: complex samples from one row (z, px) to the next (ny + padding)
     int xk0, xkn;     // paired layout: planes xk0 .. xk0 + xkn - 1 of a y / z launch (all of them, or one chunk of the blocked chain)
     int yz0;          // forward y pass: first z plane of the launch (a z chunk of the sharded step; multiple of the planes per work-group)
+    // order of the x positions of the spectrum arrays: 0 = position p holds working index p of the x transform; 1 = the low radix-8
+    // digit rotated to the top, p = (w & 7) * (hx / 8) + (w >> 3), so that a lane of the fused x pass holds the eight points of a
+    // bottom butterfly in the registers of its global access (k_x_fused_pipe; x_rotated() picks the shapes)
+    int xrot;
 };
 
 // Padded mode: the caller's volume (extents n) sits at offset o inside the transform grid; the x passes apply the boundary

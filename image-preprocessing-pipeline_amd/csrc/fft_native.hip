@@ -20,7 +20,8 @@
 //
 // Forward transforms are decimation-in-frequency (natural in, permuted out), inverse ones decimation-in-time
 // (permuted in, natural out), so no reordering pass exists: frequency-domain arrays simply live in permuted
-// positions (px, py, pz) and the OTF is built by the pipeline itself in that order (k_z_conv<BUILD>).
+// positions (px, py, pz) and the OTF is built by the pipeline itself in that order (k_z_conv<BUILD>).  (x of 2048 and 4096 samples:
+// the positions are rotated once more, so that the bottom super-stage of the fused x pass needs no LDS -- x_rotated().)
 // Each transform runs inside LDS as super-stages of 3 fused radix-2 stages held in registers (8 points per lane);
 // see "LDS image", "super-stage chains" and the pipelined kernels below for how the LDS, VALU and HBM phases are
 // kept conflict-free, short and overlapped.
@@ -67,7 +68,13 @@ __device__ __forceinline__ int phys(int i) {
 }
 // Rows: the transposed accesses of the x and z passes put `hp` row pairs x (32 / hp) consecutive elements into one lane group
 // (16 / hp for a store); row 2 rp (+1) is XOR-ed with a mask that spreads the rp bits over the banks the elements leave free.
+// hp | kRowsRot (the fused x pass on the rotated x order, hp = 8 or 4): a lane of the transposed accesses touches the eight
+// NEIGHBOURING elements 8 a .. 8 a + 7, one per instruction, and a lane group holds 32 / hp (16 / hp) consecutive a: the elements of
+// an instruction differ in bits 3.. and the rp bits go to the low bits, which they leave free (bit 3 maps to slot bit 3, bit 4 to
+// 0b11111, bit 5 to 0b01101: with 0b00001 .. 0b00100 for rp they are linearly independent, so the slots differ mod 32).
+constexpr int kRowsRot = 256;
 __device__ __forceinline__ int rmask(int row, int hp) {
+    if (hp & kRowsRot) return (row >> 1) & ((hp & (kRowsRot - 1)) - 1);
     const int rp = (row >> 1) & (hp - 1);
     const int s = hp == 8 ? 1 : hp == 4 ? 2 : hp == 2 ? 3 : 0;
     return (rp << s) ^ ((rp & 1) << 4);
@@ -141,6 +148,21 @@ __device__ __forceinline__ int mirror_pos(int p, int n, int l2, int r3) {
     const int k = pos2freq(p, l2, r3);
     return freq2pos(k == 0 ? 0 : n - k, l2, r3);
 }
+// x positions (NativeDims::xrot): the index w the x transform works with ("working index": w = freq2pos(xk) of the rule above) sits
+// at position w, or -- rotated order -- at (w & 7) * (Hx / 8) + (w >> 3).  The eight points 8a .. 8a + 7 of a bottom radix-8
+// butterfly then lie Hx / 8 positions apart, which is the stride of the eight items a lane of k_x_fused_pipe loads and stores.
+// The shapes that take the rotated order: power-of-two rows whose tile is eight float4 per lane with that stride.
+__host__ __device__ constexpr bool x_rotated(int lhx2, int r3) { return r3 == 1 && (lhx2 == 10 || lhx2 == 11); }
+// (branch-free: digit width r = 3 and shift s = lhx2 - 3 when rotated, both 0 otherwise -- then both maps are the identity)
+__device__ __forceinline__ int x_work2pos(int w, const NativeDims& d) {
+    const int r = 3 * d.xrot, s = d.xrot * (d.lhx2 - 3);
+    return ((w & ((1 << r) - 1)) << s) | (w >> r);
+}
+__device__ __forceinline__ int x_pos2work(int p, const NativeDims& d) {
+    const int r = 3 * d.xrot, s = d.xrot * (d.lhx2 - 3);
+    return ((p & ((1 << s) - 1)) << r) | (p >> s);
+}
+__device__ __forceinline__ int x_freq2pos(int k, const NativeDims& d) { return x_work2pos(freq2pos(k, d.lhx2, d.r3x), d); }
 __device__ __forceinline__ int y_pos2freq(int p, const NativeDims& d) { return pos2freq(p, d.ly2, d.r3); }
 __device__ __forceinline__ int y_mirror_pos(int p, const NativeDims& d) { return mirror_pos(p, d.ny, d.ly2, d.r3); }
 
@@ -650,7 +672,7 @@ __global__ __launch_bounds__(kThreadsXZ, kWavesXZ) void k_x_forward(const float*
 #pragma unroll MI_FFT_UNROLL
     for (int i = threadIdx.x; i < hp * Hx; i += kThreadsXZ) {
         const int px = i / hp, rp = i - px * hp;
-        const int c0 = cell(2 * rp, pitch, hp, px);
+        const int c0 = cell(2 * rp, pitch, hp, x_pos2work(px, d));
         const float2 a = tile[c0], b = tile[c0 + pitch];
         dst[(size_t)px * rowq + rp] = make_float4(a.x, a.y, b.x, b.y);
     }
@@ -774,7 +796,7 @@ __global__ __launch_bounds__(kThreadsY, 4) void k_y_pair(const float2* __restric
     } else if (z0 >= d.z_out_hi || z0 + zper <= d.z_out_lo) {
         return;                       // planes the crop drops
     }
-    const int pxA = freq2pos(xk, d.lhx2, d.r3x), pxB = freq2pos(xk == 0 ? 0 : Hx - xk, d.lhx2, d.r3x);
+    const int pxA = x_freq2pos(xk, d), pxB = x_freq2pos(xk == 0 ? 0 : Hx - xk, d);
     const bool self = pxA == pxB;
     // LDS row c of the tile: side c & 1, plane z0 + (c >> 1)
     // x side ([z][px][py], whole columns): float4 q of column c = positions 2 q, 2 q + 1
@@ -956,8 +978,8 @@ __global__ __launch_bounds__(kThreadsXZ, kWavesXZ) void k_z_conv(const float2* _
     const int plane = blockIdx.x / ytiles;
     const int py0 = (blockIdx.x % ytiles) * TL;
     const int xk = plane;
-    const int px = freq2pos(xk, d.lhx2, d.r3x);
-    const int pxB = freq2pos(xk == 0 ? 0 : Hx - xk, d.lhx2, d.r3x);
+    const int px = x_freq2pos(xk, d);
+    const int pxB = x_freq2pos(xk == 0 ? 0 : Hx - xk, d);
     // mirror block of py positions: an aligned block of TL positions maps onto an aligned block (within one power-of-two
     // sub-block: low bits of the frequency fixed -> low bits of its negative fixed)
     const int pyB_any = y_mirror_pos(py0, d);
@@ -1126,8 +1148,8 @@ __global__ __launch_bounds__(kThreadsXZ, kWavesXZ) void k_z_conv_pipe(const floa
         Where w;
         w.plane = t / ytiles;
         w.py0 = (t - w.plane * ytiles) * TL;
-        w.px = freq2pos(w.plane, d.lhx2, d.r3x);
-        w.pxB = freq2pos(w.plane == 0 ? 0 : Hx - w.plane, d.lhx2, d.r3x);
+        w.px = __builtin_amdgcn_readfirstlane(x_freq2pos(w.plane, d));
+        w.pxB = __builtin_amdgcn_readfirstlane(x_freq2pos(w.plane == 0 ? 0 : Hx - w.plane, d));
         w.pyB0 = y_mirror_pos(w.py0, d) & ~(TL - 1);
         return w;
     };
@@ -1580,7 +1602,7 @@ __global__ __launch_bounds__(kThreadsXZ, kWavesXZ) void k_x_inverse(const float2
     for (int i = threadIdx.x; i < hp * Hx; i += kThreadsXZ) {
         const int px = i / hp, rp = i - px * hp;
         const float4 v = src[(size_t)px * rowq + rp];
-        const int c0 = cell(2 * rp, pitch, hp, px);
+        const int c0 = cell(2 * rp, pitch, hp, x_pos2work(px, d));
         tile[c0] = make_float2(v.x, v.y);
         tile[c0 + pitch] = make_float2(v.z, v.w);
     }
@@ -1678,7 +1700,7 @@ __global__ __launch_bounds__(kThreadsXZ, kWavesXZ) void k_x_inverse(const float2
 #pragma unroll MI_FFT_UNROLL
         for (int i = threadIdx.x; i < hp * Hx; i += kThreadsXZ) {
             const int px = i / hp, rp = i - px * hp;
-            const int c0 = cell(2 * rp, pitch, hp, px);
+            const int c0 = cell(2 * rp, pitch, hp, x_pos2work(px, d));
             const float2 a = tile[c0], b = tile[c0 + pitch];
             sdst[(size_t)px * rowq + rp] = make_float4(a.x, a.y, b.x, b.y);
         }
@@ -1711,6 +1733,16 @@ __global__ __launch_bounds__(kThreadsXZ, kWavesXZ) void k_x_fused_pipe(const flo
     constexpr int NPF = (NQ + kThreadsXZ - 1) / kThreadsXZ;
     constexpr int pitch = row_pitch(Hx);
     constexpr int P = kThreadsXZ / hp;  // item j of a lane in the transposed view: column px0 + j * P, row pair rp
+    // REG (the rotated x order, NativeDims::xrot): column px0 + j * P holds working index 8 px0 + j, so the eight items of a lane are
+    // the points of one bottom radix-8 butterfly (stages 0-2: compile-time twiddles, no table) of each of its two rows.  That
+    // super-stage -- the first of the inverse transform, the last of the forward one -- runs on the registers the loads arrive in
+    // and the stores leave from: the fill writes its results to the slots 8 px0 .. 8 px0 + 7 and the inverse chain starts at stage
+    // 3, the forward chain stops there and the drain finishes the transform (one LDS round trip fewer per direction; the z pass
+    // does the same with its top super-stage, k_z_pair_pipe).  The arithmetic is that of super_stage<.., 3, 0, ..>.
+    constexpr bool REG = x_rotated(LHX2, R3);
+    static_assert(!REG || (NPF == 8 && P * 8 == Hx && NQ % kThreadsXZ == 0), "rotated x order: eight items per lane, Hx / 8 apart");
+    constexpr int hpm = REG ? (hp | kRowsRot) : hp;  // row masks for the eight-neighbour accesses of the fill and the drain (rmask)
+    constexpr int REG_R = REG ? 3 : 0;
     // rows dealt to the waves: the inverse transform, the epilogue and the forward transform of a row all belong to its owner
     // and run without work-group barriers; only the transposed fill and drain are tile-wide
     constexpr bool PRIV = (TY % NW == 0) && (NQ % kThreadsXZ == 0) && (quads % 64 == 0);
@@ -1724,7 +1756,7 @@ __global__ __launch_bounds__(kThreadsXZ, kWavesXZ) void k_x_fused_pipe(const flo
     auto t_view = [&]() {
         const int tid = launder(threadIdx.x);
         const int px0 = tid / hp, rp = tid - px0 * hp;
-        return TView{(2 * rp) * pitch, phys(px0) ^ rmask(2 * rp, hp), (size_t)px0 * rowq + rp};
+        return TView{(2 * rp) * pitch, phys(REG ? 8 * px0 : px0) ^ rmask(2 * rp, hpm), (size_t)px0 * rowq + rp};
     };
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // row view, item j: PRIV: float4 u = lane + 64 j of the wave's rows -> row rl * NW + wave, quad q; else float4 tid + j * NT
@@ -1739,12 +1771,12 @@ __global__ __launch_bounds__(kThreadsXZ, kWavesXZ) void k_x_fused_pipe(const flo
             r = rl * NW + wave;                                        // scalar
             q = q0 + rv.lane;
             i = r * quads + q;
-            c = r * pitch + (rv.slot ^ swz_c(2 * q0) ^ rmask(r, hp));
+            c = r * pitch + (rv.slot ^ swz_c(2 * q0) ^ rmask(r, hpm));
         } else {
             i = rv.tid + j * kThreadsXZ;
             r = i / quads;
             q = i - r * quads;
-            c = cell(r, pitch, hp, 2 * q);
+            c = cell(r, pitch, hpm, 2 * q);
         }
     };
     // Padded grids (zero rule, data at the origin, nx a multiple of 4): row r of a tile is row y0 + r of the caller's volume when
@@ -1833,12 +1865,29 @@ __global__ __launch_bounds__(kThreadsXZ, kWavesXZ) void k_x_fused_pipe(const flo
         };
         if constexpr (MODE != 1) {
             const TView tv = t_view();
+            if constexpr (REG) {
+                float2 v[8], u[8];  // rows 2 rp and 2 rp + 1
 #pragma unroll
-            for (int j = 0; j < NPF; ++j) {
-                if (NQ % kThreadsXZ == 0 || (int)threadIdx.x + j * kThreadsXZ < NQ) {
-                    const int c0 = tv.row + (tv.slot ^ swz_c(j * P));
-                    tile[c0] = make_float2(pre[j].x, pre[j].y);
-                    tile[c0 + pitch] = make_float2(pre[j].z, pre[j].w);
+                for (int j = 0; j < 8; ++j) {
+                    v[j] = make_float2(pre[j].x, pre[j].y);
+                    u[j] = make_float2(pre[j].z, pre[j].w);
+                }
+                butterflies<3, 0, true>(v, nullptr, 0);
+                butterflies<3, 0, true>(u, nullptr, 0);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int c0 = tv.row + (tv.slot ^ j);
+                    tile[c0] = v[j];
+                    tile[c0 + pitch] = u[j];
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < NPF; ++j) {
+                    if (NQ % kThreadsXZ == 0 || (int)threadIdx.x + j * kThreadsXZ < NQ) {
+                        const int c0 = tv.row + (tv.slot ^ swz_c(j * P));
+                        tile[c0] = make_float2(pre[j].x, pre[j].y);
+                        tile[c0 + pitch] = make_float2(pre[j].z, pre[j].w);
+                    }
                 }
             }
         }
@@ -1877,11 +1926,11 @@ __global__ __launch_bounds__(kThreadsXZ, kWavesXZ) void k_x_fused_pipe(const flo
         if (R3 != 9 && !LATE_A) load_a();  // (radix-9 rows: requested behind the 9-point stage, which needs the registers)
         lds_barrier();
         if constexpr (LATE_A) {
-            lds_fft<LHX2, true, kThreadsXZ, R3, 0, TOP_LO>(tile, TY * R3, pitch, hp, PRIV, twl);
+            lds_fft<LHX2, true, kThreadsXZ, R3, REG_R, TOP_LO>(tile, TY * R3, pitch, hpm, PRIV, twl);
             load_a();
-            lds_fft<LHX2, true, kThreadsXZ, R3, TOP_LO, LHX2>(tile, TY * R3, pitch, hp, PRIV, twl);
+            lds_fft<LHX2, true, kThreadsXZ, R3, TOP_LO, LHX2>(tile, TY * R3, pitch, hpm, PRIV, twl);
         } else {
-            lds_fft<LHX2, true, kThreadsXZ, R3>(tile, TY * R3, pitch, hp, PRIV, twl);
+            lds_fft<LHX2, true, kThreadsXZ, R3, REG_R>(tile, TY * R3, pitch, hpm, PRIV, twl);
         }
         if constexpr (R3 > 1) {
             radix3_stage<R3, true, kThreadsXZ>(tile, TY, pitch, hp, PRIV, 1 << LHX2, twl + TW::r3);
@@ -1934,16 +1983,30 @@ __global__ __launch_bounds__(kThreadsXZ, kWavesXZ) void k_x_fused_pipe(const flo
             stage_sync(PRIV);
         }
         if (MODE == 0 && R3 == 9 && tn < ntiles) load_T(tn);
-        lds_fft<LHX2, false, kThreadsXZ, R3>(tile, TY * R3, pitch, hp, PRIV, twl);
+        lds_fft<LHX2, false, kThreadsXZ, R3, 0, LHX2 - REG_R>(tile, TY * R3, pitch, hpm, PRIV, twl);
         if (PRIV) lds_barrier();  // rows complete for everybody before the transposed drain
         const TView tv = t_view();
         float4* sdst = reinterpret_cast<float4*>(S_next + tile_base(t)) + tv.off;
+        if constexpr (REG) {
+            float2 v[8], u[8];
 #pragma unroll
-        for (int j = 0; j < NPF; ++j) {
-            if (NQ % kThreadsXZ == 0 || (int)threadIdx.x + j * kThreadsXZ < NQ) {
-                const int c0 = tv.row + (tv.slot ^ swz_c(j * P));
-                const float2 a = tile[c0], b = tile[c0 + pitch];
-                sdst[(size_t)(j * P) * rowq] = make_float4(a.x, a.y, b.x, b.y);
+            for (int j = 0; j < 8; ++j) {
+                const int c0 = tv.row + (tv.slot ^ j);
+                v[j] = tile[c0];
+                u[j] = tile[c0 + pitch];
+            }
+            butterflies<3, 0, false>(v, nullptr, 0);
+            butterflies<3, 0, false>(u, nullptr, 0);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) sdst[(size_t)(j * P) * rowq] = make_float4(v[j].x, v[j].y, u[j].x, u[j].y);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NPF; ++j) {
+                if (NQ % kThreadsXZ == 0 || (int)threadIdx.x + j * kThreadsXZ < NQ) {
+                    const int c0 = tv.row + (tv.slot ^ swz_c(j * P));
+                    const float2 a = tile[c0], b = tile[c0 + pitch];
+                    sdst[(size_t)(j * P) * rowq] = make_float4(a.x, a.y, b.x, b.y);
+                }
             }
         }
         if (dyn && threadIdx.x == 0) s_next_tile = fetched;
@@ -2042,6 +2105,7 @@ int NativeFft::init(hipStream_t s, const int F[3], bool explicit_adjoint) {
     split_axis(F[1], &dims.r3, &dims.ly2, true);  // (the y axis also takes 5 * 2^a: 320 rows of a slab rank instead of 384)
     split_axis(F[2], &dims.r3z, &dims.lz2);
     dims.hx = Hx;
+    dims.xrot = x_rotated(dims.lhx2, dims.r3x) ? 1 : 0;
     dims.ny = F[1];
     dims.nz = F[2];
     dims.ty = std::min(x_tile_rows(Hx), F[1]);
@@ -2708,7 +2772,10 @@ int NativeFft::x_inverse(hipStream_t s, float* out, int epi_kind, const ConvEpil
     // and the caller's rows are whole float4 groups
     const bool pad_pipe = pw.on && can_fuse() && pipe_ok() && pw.o[0] == 0 && pw.o[1] == 0 && pw.o[2] == 0 && pw.n[0] % 4 == 0 &&
                           ((uintptr_t)epi.a % 16) == 0 && ((uintptr_t)out % 16) == 0 && !(part && part->mode != 0);
-    if (fuse_forward && (splits() || pad_pipe)) {
+    // (MI_FFT_NO_XPIPE=1 sends a whole fused pass through k_x_inverse too -- every stage in LDS, same arithmetic: the reference route
+    // of tests/test_gpu_x_register_stage.py; a subset of the tiles exists only in the persistent kernel)
+    const bool whole = !(part && part->mode != 0);
+    if (fuse_forward && (splits() || pad_pipe) && !(whole && std::getenv("MI_FFT_NO_XPIPE") != nullptr)) {
         TileSelect sel{};
         int per = M / dims.ty, planes = L;
         if (pad_pipe) {  // only the tiles that hold rows of the caller's volume
