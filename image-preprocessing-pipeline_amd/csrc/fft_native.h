@@ -1,4 +1,6 @@
-// Internal interface of the hand-written FFT convolution pipeline (fft_native.hip).
+// Internal interface of the hand-written FFT convolution pipeline: the plan (fft_native.hip), its passes (fft_native_x.hip,
+// fft_native_yz.hip; device building blocks in fft_native_dev.h) and where its arrays lie
+// (fft_native_place.hip).
 #pragma once
 #include <vector>
 #include <algorithm>
@@ -45,17 +47,6 @@ struct TileSelect {
     int z0 = 0, nz = 0;  // only the planes [z0, z0 + nz) (nz = 0: all): the z-chunked halo exchange runs the edge tiles chunk by chunk
 };
 
-// a device address range backed by physical chunks that were created one by one and mapped in a chosen order (HIP virtual memory)
-struct VmmRange {
-    void* va = nullptr;
-    size_t bytes = 0, chunk = 0;
-    bool mapped = false;
-    std::vector<hipMemGenericAllocationHandle_t> h;
-    int alloc(size_t n, size_t chunk_bytes, int order);
-    void release();
-    ~VmmRange() { release(); }
-};
-
 // While one of these exists on a thread, the contexts that thread creates take their spectrum arrays as they come instead of placing
 // them by trial (NativeFft::init): the whole-loop entry points (mi_decon, mi_decon_plan_run, mi_rl_fft) run a handful of iterations per
 // context, the trial costs 0.5 s, holds six candidates of the arrays, is serialised per device and trims the pool -- with five
@@ -66,14 +57,14 @@ struct NoPlacementTrial {
     ~NoPlacementTrial();
     NoPlacementTrial(const NoPlacementTrial&) = delete;
     NoPlacementTrial& operator=(const NoPlacementTrial&) = delete;
+    static bool active();  // one exists on the calling thread
 };
 
 struct NativeFft {
+    // ---- the plan (fft_native.hip)
     NativeDims dims{};
-    PadWindow pw{};
     DevBuf S, G, G_adj, tw;  // S: both spectrum arrays, S first
-    float2* t_spec = nullptr;  // the second spectrum array T (inside S's allocation, or T2 when the arrays were placed by trial)
-    DevBuf T2, S_alt;  // S_alt: a second buffer for S, kept until the caller's volume is known (settle_s)
+    float2* t_spec = nullptr;  // the second spectrum array T (inside S's allocation, or place.T2 when the arrays were placed by trial)
     DevBuf Gr, Gr_adj, ph;  // real form of the OTF(s) + phase tables (symmetric PSFs), see try_real_otf
     bool real_otf = false;
     bool have_adj = false;  // adjoint = second OTF (G_adj) instead of conj(G)
@@ -81,19 +72,8 @@ struct NativeFft {
     const float2* tw_y = nullptr;
     const float2* tw_z = nullptr;
     size_t n_cplx = 0;
+    size_t spec_bytes = 0;
     int n_cu = 256;  // persistent kernels launch one work-group per CU
-    std::vector<float> placement_ms;  // forward y pass on each candidate placement of the spectrum arrays (init)
-    int placement_kept = -1;
-    // x launches that run beside a halo exchange (part 2 of a sharded step): compute units left free for the collective's
-    // kernels, tiles handed out by a device counter instead of a fixed stride (mi_rl_set_overlap)
-    int overlap_free_cus = 0;
-    bool overlap_dynamic = true;
-    bool x_dynamic = true;   // every other persistent x launch
-    DevBuf ctr;
-    bool z_dynamic = true;   // the paired z pass takes its tiles from a counter too
-    int ctr_slot = 0;
-    int persistent_grid(hipStream_t s, int ntiles, bool overlapped, unsigned* grid, int** ctr_out);
-    VmmRange vmm;  // probe builds, MI_FFT_VMM: the spectrum arrays as a range mapped chunk by chunk
     ~NativeFft();
 
     static bool supported(const int F[3]);
@@ -109,7 +89,6 @@ struct NativeFft {
     float4* otf() { return G.as<float4>(); }
     // after build_otf: switch to the real OTF form when the PSF allows it (delta: centre offset from the grid origin)
     int try_real_otf(hipStream_t s, const int delta[3]);
-    bool z_pipelined() const;
     float* scratch() { return reinterpret_cast<float*>(t_spec); }  // F floats, free between convolutions
     // after the OTFs are built: volumes handed to conv / iterate have extents n (x, y, z) and are padded on the fly
     void set_window(const int n[3], const int o[3], const int rep[3], const int k[3]);
@@ -118,33 +97,68 @@ struct NativeFft {
     // `conj_otf` selects the adjoint: conj(OTF), or the explicit adjoint OTF when one was given
     // n fused RL iterations on bl in place (lambda = 0, no regularisation step in between)
     int iterate(hipStream_t s, float* bl, int n_iters);
-    int time_pass(hipStream_t s, int which, const float* bl, int reps, float* avg_ms);
     size_t spectrum_bytes() const { return spec_bytes; }   // one of the two spectrum arrays
-    void settle_before_update();
-    int settle_decide(hipStream_t s);
-    // the spare buffer for S goes back to the driver (every consumer of S other than iterate() calls this first: the sharded steps of
-    // the slab driver, single convolutions -- a C4-shaped rank carried 9.7 GB of it for the whole run)
-    int release_spare();
-    int alt_phase = 0;                 // 0 / 1: the next timed update launch writes the first / second S buffer; 2: decide; 3: settled
-    hipEvent_t alt_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    int time_between(hipStream_t s, int which, const float2* src, float2* dst, float* bl, int reps, float* avg_ms);
-    size_t spec_bytes = 0;
+    size_t spectrum_row_floats() const { return (size_t)2 * dims.nz * dims.hx; }
+    size_t device_bytes() const {
+        return S.bytes + place.T2.bytes + place.S_alt.bytes + G.bytes + G_adj.bytes + Gr.bytes + Gr_adj.bytes + ph.bytes + tw.bytes;
+    }
+
+    // ---- the passes (fft_native_x.hip, fft_native_yz.hip)
+    int x_forward(hipStream_t s, const float* in);
+    int middle(hipStream_t s, bool conj_otf);
+    int y_pass(hipStream_t s, bool inverse, bool paired, const float2* src = nullptr, float2* dst = nullptr, int xk0 = 0, int xkn = -1);
+    int z_conv(hipStream_t s, bool conj_otf, const float2* src = nullptr, float2* dst = nullptr, int xk0 = 0, int xkn = -1);
+    int x_inverse(hipStream_t s, float* out, int epi_kind, const ConvEpilogue& epi, bool fuse_forward, const TileSelect* part = nullptr);
+    bool z_pipelined() const;
     // rows [y0, y0 + rows) of S (the x-transformed input of the next convolution): dir 0 pack into buf, 1 unpack from buf, 2 zero
     // (z0, nzc: only the planes [z0, z0 + nzc), which keep their place in the packed buffer; nzc = 0: all)
     int spectrum_rows(hipStream_t s, int y0, int rows, float2* buf, int dir, int z0 = 0, int nzc = 0);
     // forward y pass of the planes [z0, z0 + nzc) only (both layouts); z0 and nzc multiples of y_z_granule()
     int y_forward_planes(hipStream_t s, int z0, int nzc);
     int y_z_granule() const { return dims.paired ? std::max(1, dims.tc / 2) : 1; }
-    size_t spectrum_row_floats() const { return (size_t)2 * dims.nz * dims.hx; }
-    int x_forward(hipStream_t s, const float* in);
-    int middle(hipStream_t s, bool conj_otf);
-    int y_pass(hipStream_t s, bool inverse, bool paired, const float2* src = nullptr, float2* dst = nullptr, int xk0 = 0, int xkn = -1);
-    int z_conv(hipStream_t s, bool conj_otf, const float2* src = nullptr, float2* dst = nullptr, int xk0 = 0, int xkn = -1);
-    int x_inverse(hipStream_t s, float* out, int epi_kind, const ConvEpilogue& epi, bool fuse_forward, const TileSelect* part = nullptr);
+
+    // ---- pad window and tiles of the x passes
+    PadWindow pw{};
     bool pipe_ok() const;  // the fused x pass can run as the persistent pipelined kernel
     bool splits() const;   // ... and a subset of its tiles (unpadded grids)
     TileSelect edge_tiles(int mode, int a0, int a1, int b0, int b1) const;
-    size_t device_bytes() const { return S.bytes + T2.bytes + S_alt.bytes + G.bytes + G_adj.bytes + Gr.bytes + Gr_adj.bytes + ph.bytes + tw.bytes; }
+    // padded grids take the persistent x kernels too: zero rule, data at the origin, whole float4 rows and what the call site asks
+    // of its pointers (`aligned`)
+    bool pad_pipe(bool aligned) const;
+    // tiles of a pipelined x launch: those of the pad window (`padded`), else the caller's subset `part`, else all
+    int pipe_tiles(bool padded, const TileSelect* part, TileSelect* sel, int* ntiles) const;
+    // k_x_fused_pipe<.., mode> on those tiles (mode 0 fused, 1 forward only, 2 inverse only)
+    int x_pipelined(hipStream_t s, int mode, const float2* T, float* out, const ConvEpilogue& epi, int ek, const TileSelect& sel, int ntiles);
+    // x launches that run beside a halo exchange (part 2 of a sharded step): compute units left free for the collective's
+    // kernels, tiles handed out by a device counter instead of a fixed stride (mi_rl_set_overlap)
+    int overlap_free_cus = 0;
+    bool overlap_dynamic = true;
+    bool x_dynamic = true;   // every other persistent x launch
+    DevBuf ctr;
+    bool z_dynamic = true;   // the paired z pass takes its tiles from a counter too
+    int ctr_slot = 0;
+    int persistent_grid(hipStream_t s, int ntiles, bool overlapped, unsigned* grid, int** ctr_out);
+
+    // ---- where the spectrum arrays lie (fft_native_place.hip)
+    struct Placement {
+        DevBuf T2, S_alt;  // S_alt: a second buffer for S, kept until the caller's volume is known (settle_decide)
+        int alt_phase = 0;  // 0 / 1: the next timed update launch writes the first / second S buffer; 2: decide; 3: settled
+        hipEvent_t alt_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        std::vector<float> placement_ms;  // cost of each candidate placement of the spectrum arrays (place_by_trial)
+        int placement_kept = -1;
+    } place;
+    // the two arrays on the best ordered pair of several buffers allocated side by side (init: large plans only; gap: bytes between
+    // S and T in init's single allocation, which stands when the candidates do not fit)
+    int place_by_trial(hipStream_t s, size_t gap);
+    void settle_before_update();
+    int settle_decide(hipStream_t s);
+    // the spare buffer for S goes back to the driver (every consumer of S other than iterate() calls this first: the sharded steps of
+    // the slab driver, single convolutions -- a C4-shaped rank carried 9.7 GB of it for the whole run)
+    int release_spare();
+
+    // ---- timing (bench.py's roofline leg; fft_native_place.hip)
+    int time_pass(hipStream_t s, int which, const float* bl, int reps, float* avg_ms);
+    int time_between(hipStream_t s, int which, const float2* src, float2* dst, float* bl, int reps, float* avg_ms);
 };
 
 }  // namespace mi

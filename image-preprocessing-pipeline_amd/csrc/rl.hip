@@ -543,9 +543,9 @@ extern "C" int mi_rl_fft_placement(mi_rl_ctx* ctx, float* cost_ms, int cap, int*
     *n = 0;
     *kept = -1;
     if (!(ctx->engine == MI_ENGINE_FFT && ctx->fft && ctx->fft->native)) return MI_OK;
-    const auto& ms = ctx->fft->native->placement_ms;
+    const auto& ms = ctx->fft->native->place.placement_ms;
     *n = (int)ms.size();
-    *kept = ctx->fft->native->placement_kept;
+    *kept = ctx->fft->native->place.placement_kept;
     for (int i = 0; i < *n && i < cap; ++i) cost_ms[i] = ms[i];
     return MI_OK;
 }

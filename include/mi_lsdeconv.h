@@ -24,7 +24,7 @@ typedef enum {
 typedef enum {
     MI_ENGINE_AUTO = 0,   /* cost model on PSF taps / volume size (mi_engine_select) */
     MI_ENGINE_DIRECT = 1, /* LDS-tiled direct convolution (fp32 FMA); three 1-D passes for rank-1 PSFs (mi_rl_separable) */
-    MI_ENGINE_FFT = 2     /* FFT convolution on the grid the boundary rule requires: hand-written pipeline (fft_native.hip), rocFFT
+    MI_ENGINE_FFT = 2     /* FFT convolution on the grid the boundary rule requires: hand-written pipeline (fft_native*.hip), rocFFT
                              for extents it does not take */
     /* (a matrix-core direct engine was prototyped and measured -- banded-Toeplitz v_mfma_f32_16x16x4_f32, bit-identical results,
        70 ms against 58 ms of the fp32 FMA engine on BASELINE config 2: profiles/mfma_toeplitz_probe.hip,
@@ -212,7 +212,7 @@ int mi_rl_time_pass(mi_rl_ctx* ctx, void* stream, int which, const float* bl, in
 size_t mi_rl_fft_spectrum_bytes(mi_rl_ctx* ctx);
 int mi_rl_time_between(mi_rl_ctx* ctx, void* stream, int which, const void* src, void* dst, float* bl, int reps, float* avg_ms);
 /* Measurement hook: how the spectrum arrays of the native FFT pipeline were placed when the context was created (candidates
- * allocated side by side, "4 y passes + update launch" timed on each, the fastest kept: csrc/fft_native.hip, NativeFft::init).
+ * allocated side by side, "4 y passes + update launch" timed on each, the fastest kept: csrc/fft_native_place.hip, NativeFft::place_by_trial).
  * Writes up to `cap` candidate costs in ms to cost_ms -- one per ordered pair (S, T) of the buffers tried, S slowest --, their
  * number to *n (0: a plain allocation) and the index of the kept pair to *kept.  No reference counterpart (the reference allocates inside MATLAB's gpuArray). */
 int mi_rl_fft_placement(mi_rl_ctx* ctx, float* cost_ms, int cap, int* n, int* kept);
