@@ -91,6 +91,24 @@ class LightsheetInfo(C.Structure):
         "bg_zero_last_row", "bg_zero_last_col", "integer_mode", "max_batch")] + [("scratch_bytes_per_tile", C.c_size_t)]
 
 
+ISO_MAX_STEPS = 32  # MI_ISO_MAX_STEPS
+
+
+class IsodownParams(C.Structure):
+    """mi_isodown_params (include/mi_isodown.h)."""
+    _fields_ = [("voxel_y", C.c_double), ("voxel_x", C.c_double), ("target_voxel", C.c_double), ("alternating", C.c_int),
+                ("z_rounds", C.c_int), ("out_dtype", C.c_int), ("max_group", C.c_int)]
+
+
+class IsodownInfo(C.Structure):
+    """mi_isodown_info (include/mi_isodown.h)."""
+    _fields_ = [("ny", C.c_int), ("nx", C.c_int), ("target_ny", C.c_int), ("target_nx", C.c_int), ("rounds_y", C.c_int),
+                ("rounds_x", C.c_int), ("nsteps", C.c_int), ("step_axis", C.c_int * ISO_MAX_STEPS), ("step_method", C.c_int * ISO_MAX_STEPS),
+                ("step_extent", C.c_int * ISO_MAX_STEPS), ("ky", C.c_int), ("kx", C.c_int), ("halved_ny", C.c_int), ("halved_nx", C.c_int),
+                ("sigma_y", C.c_double), ("sigma_x", C.c_double), ("radius_y", C.c_int), ("radius_x", C.c_int), ("taps_y", C.c_int),
+                ("taps_x", C.c_int), ("tile_ny", C.c_int), ("tile_nx", C.c_int), ("lds_steps", C.c_int), ("scratch_bytes_per_slice", C.c_size_t)]
+
+
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _ip = C.POINTER(C.c_int)
 
@@ -194,6 +212,16 @@ SIGNATURES = {
     "mi_lightsheet_plan_info": (_i, [_vp, C.POINTER(LightsheetInfo)]),
     "mi_lightsheet_run": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64]),
     "mi_lightsheet_local_percentile": (_i, [_i, _vp, _vp, _i, _i, _i, C.c_int64] + [_i] * 6 + [C.c_double, _i, _vp, _i]),
+    # mi_isodown.h
+    "mi_isodown_derive": (_i, [_i, _i, C.c_double, C.c_double, C.c_double, _i, C.POINTER(IsodownInfo)]),
+    "mi_isodown_plan_create": (_i, [_i, _i, _i, _i, C.POINTER(IsodownParams), C.POINTER(_vp)]),
+    "mi_isodown_plan_destroy": (_i, [_vp]),
+    "mi_isodown_plan_info": (_i, [_vp, C.POINTER(IsodownInfo)]),
+    "mi_isodown_halve": (_i, [_vp, _vp, _vp, C.c_int64, _vp, _vp]),
+    "mi_isodown_planes": (_i, [_vp, _vp, _vp, C.c_int64, _vp]),
+    "mi_isodown_run": (_i, [_vp, _vp, _vp, C.c_int64, _vp, _vp]),
+    "mi_isodown_reduce_z": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mi_resize_antialias": (_i, [_i, _vp, _vp, _i, _ip, _ip, _vp]),
     # mi_crossmips.h
     "mi_ncc_default_params": (None, [_i, _i, _i, C.POINTER(NccParams)]),
     "mi_ncc_mips": (_i, [_i, _vp, _vp, _vp] + [_i] * 10 + [C.POINTER(NccParams), C.POINTER(NccDescr)]),
