@@ -48,6 +48,7 @@ static bool split_axis(int n, int* r3, int* l2, bool five = false) {
 }
 
 static const int kMaxZ = 2304;  // 2 * TL >= 4 rows of the z pass must fit the LDS tile
+static const int kMaxLen = 9 << 9;  // the longest length of split_axis
 
 bool NativeFft::supported(const int F[3]) {
     // x: real length 2 * Hx, the transform runs on Hx complex points
@@ -56,13 +57,16 @@ bool NativeFft::supported(const int F[3]) {
 }
 
 int NativeFft::good_size(int n, int axis) {
+    // (the searches end at the longest length split_axis takes, 9 * 2^9: beyond it there is no extent, and the answer is 0)
     int r3, l2;
     if (axis == 0) {
-        for (int h = n < 16 ? 8 : (n + 1) / 2;; ++h)
+        for (int h = n < 16 ? 8 : (n + 1) / 2; h <= kMaxLen; ++h)
             if (split_axis(h, &r3, &l2)) return 2 * h;
+        return 0;
     }
-    for (int m = n < 8 ? 8 : n;; ++m)
-        if (split_axis(m, &r3, &l2, axis == 1)) return (axis == 2 && m > kMaxZ) ? 0 : m;
+    for (int m = n < 8 ? 8 : n; m <= (axis == 2 ? kMaxZ : kMaxLen); ++m)
+        if (split_axis(m, &r3, &l2, axis == 1)) return m;
+    return 0;
 }
 
 int NativeFft::init(hipStream_t s, const int F[3], bool explicit_adjoint) {

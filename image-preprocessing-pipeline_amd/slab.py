@@ -335,6 +335,8 @@ class SlabRL:
         rows = self.n_loc + 2 * self.h
         # local extent the FFT pipeline takes natively (2^a * {1,3,5,9} on this axis); the rows behind the upper halo stay zero
         self.rows = int(capi.lib().mi_fft_good_size(rows, 1)) if ops is None else rows
+        if self.rows <= 0:
+            raise ValueError(f"slab of {rows} rows with its halos is longer than any extent the FFT pipeline takes; use more ranks")
         bxz = BOUNDARY_CIRCULAR if flavour == "fft" else BOUNDARY_ZERO
         # y is "circular on the local extent": wrap-around only ever reaches halo / padding rows
         boundary_xyz = (bxz, BOUNDARY_CIRCULAR, bxz)

@@ -1,5 +1,7 @@
-"""GPU: the hand-written FFT convolution pipeline (fft_native.hip: power-of-two shapes) against the oracle, against
-scipy's circular convolution and against the rocFFT route of the same engine (MI_FFT_ROCFFT=1)."""
+"""GPU: the hand-written FFT convolution pipeline (fft_native.hip: extents 2^a, 3 * 2^a and 9 * 2^a, on y also 5 * 2^a) against the
+oracle, against scipy's circular convolution and against the rocFFT route of the same engine (MI_FFT_ROCFFT=1), in the spatial
+domain.  Every length the plan takes, checked bin by bin in the frequency domain: tests/test_gpu_fft_spectral.py (the complete
+list is NATIVE_LENGTHS of tests/spectral_util.py)."""
 import os
 
 import numpy as np

@@ -157,6 +157,8 @@ def test_fft_good_size_per_axis():
     assert [g(n, 1) for n in (1, 8, 9, 33, 97, 130, 257, 289, 600, 1100, 1153)] == [8, 8, 16, 64, 128, 160, 288, 320, 640, 1152, 1280]
     assert [g(n, 0) for n in (10, 17, 70, 193, 200, 600, 2100)] == [16, 32, 128, 256, 256, 768, 2304]
     assert [g(n, 2) for n in (61, 100, 530, 2049, 2305)] == [64, 128, 576, 2304, 0]
+    # past the longest extent of an axis (9 * 2^9; x twice that) there is none: 0, as include/mi_lsdeconv.h says
+    assert [g(9216, 0), g(9217, 0), g(4608, 1), g(4609, 1), g(100000, 1), g(4609, 2)] == [9216, 0, 4608, 0, 0, 0]
     for axis in range(3):
         for n in range(1, 700, 7):
             m = g(n, axis)
