@@ -193,7 +193,9 @@ __global__ __launch_bounds__(kThreads) void k_sub_dark(const float* __restrict__
 __global__ __launch_bounds__(kThreads) void k_sumsq(const float* __restrict__ x, size_t n, double* __restrict__ out) {
     size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
     double acc = 0.0;
-    size_t n4 = n / 4;
+    // (internal callers -- the stop test of the deconvolution loops -- pass the caller's volume as it is: element-wise when its
+    // base is not 16-byte aligned; mi_norm2 itself refuses such a pointer)
+    size_t n4 = ((uintptr_t)x % 16) == 0 ? n / 4 : 0;
     const float4* x4 = reinterpret_cast<const float4*>(x);
     for (size_t i = tid; i < n4; i += stride) {
         float4 v = x4[i];

@@ -431,6 +431,11 @@ int FftEngine::conv(hipStream_t s, const float* in, bool adjoint, float* out, in
                            ax[2].boundary == MI_BOUNDARY_REPLICATE);
         MI_TRY(launch_check("k_stage"));
         src = real.as<float>();
+    } else if (((uintptr_t)in % 16) != 0) {
+        // rocFFT's kernels choose their own access widths: a volume whose base is only element-aligned goes through the staging
+        // volume like a padded one
+        MI_HIP(hipMemcpyAsync(real.p, in, sizeof(float) * n_real, hipMemcpyDeviceToDevice, s));
+        src = real.as<float>();
     }
     void* fin[1] = {const_cast<float*>(src)};
     void* fout[1] = {spec.p};
