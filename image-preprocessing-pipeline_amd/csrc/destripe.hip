@@ -351,11 +351,16 @@ extern "C" int mi_destripe_z(int dev, void* stream, float* bl, int nx, int ny, i
     if (levels == 0) {  // wavedec2 with zero levels: the transform is the identity, and so is the filter
         return MI_OK;
     }
-    // per level: A, H, V, D [sz_l][Y][sx_l]; the z-analysis halves ZL, ZH [sz_l][Y][sx_{l-1}] are shared by all levels
+    // per level: A, H, V, D [sz_l][Y][sx_l]; the z-analysis halves ZL, ZH [sz_l][Y][sx_{l-1}] are shared by all levels.  Level 1
+    // is the largest unless `levels` exceeds wmaxlev on an extent below lf - 1, where the coefficient count GROWS towards lf - 1
+    // from level to level ((n + lf - 1) / 2 > n for n < lf - 1)
     std::vector<DevBuf> A(levels + 1), H(levels + 1), V(levels + 1), D(levels + 1);
     DevBuf ZL, ZH;
-    MI_TRY(ZL.alloc(sizeof(float) * (size_t)sz[1] * Y * sx[0]));
-    MI_TRY(ZH.alloc(sizeof(float) * (size_t)sz[1] * Y * sx[0]));
+    size_t zhalf = 0;
+    for (int l = 1; l <= levels; ++l)  // sx[l]: ZL also serves as the notch's `corr` [sz_l][Y][sx_l]
+        zhalf = std::max(zhalf, (size_t)sz[l] * Y * (size_t)std::max(sx[l - 1], sx[l]));
+    MI_TRY(ZL.alloc(sizeof(float) * zhalf));
+    MI_TRY(ZH.alloc(sizeof(float) * zhalf));
     for (int l = 1; l <= levels; ++l) {
         const size_t bytes = sizeof(float) * (size_t)sz[l] * Y * sx[l];
         MI_TRY(A[l].alloc(bytes));
