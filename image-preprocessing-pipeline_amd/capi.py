@@ -123,6 +123,7 @@ SIGNATURES = {
     "mi_conv3d_replicate": (_i, [_i, _vp, _vp, _vp, _vp] + [_i] * 6),
     "mi_conv3d": (_i, [_i, _vp, _vp, _vp, _vp] + [_i] * 8),
     "mi_gauss3d_inplace": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, C.POINTER(C.c_float), _ip]),
+    "mi_gauss3d_route": (_i, [_i, _i, _i, C.POINTER(C.c_float), _ip]),
     "mi_edgetaper3d": (_i, [_i, _vp, _vp, _vp, _vp] + [_i] * 6),
     "mi_otf": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _f]),
     "mi_u16_to_f32": (_i, [_i, _vp, _vp, _vp, _sz, _f]),

@@ -79,7 +79,10 @@ __global__ __launch_bounds__(64 * GXY_WAVES) void k_gauss_xy(const float* __rest
     };
 #pragma unroll
     for (int u = 0; u < GXY_PF; ++u) fetch(ya - ry + u, pa[u], pb[u]);
-    for (int p = ya - ry; p < yb + ry; ++p) {
+    // output row yo is emitted at walk position yo + lead, when the ring holds rows yo - ry .. yo - ry + ty.n - 1: the reference's
+    // window (offset s - klen / 2, gauss3d_gpu.cu:124-135); lead == ry for odd tap counts, ry - 1 for even ones
+    const int lead = ty.n - 1 - ry;
+    for (int p = ya - ry; p < yb + lead; ++p) {
         // stage the clamped row segment: sample i is x = x0 - rx + i
         rb[lane] = pa[0];
         if (has_b) rb[lane + 64] = pb[0];
@@ -90,10 +93,10 @@ __global__ __launch_bounds__(64 * GXY_WAVES) void k_gauss_xy(const float* __rest
         float xf = 0.0f;
         for (int s = 0; s < tx.n; ++s) xf = fmaf(rb[lane + s], tx.w[s], xf);
         ring[slot * 64 + lane] = xf;  // private column of this lane: no barrier needed for the ring
-        const int yo = p - ry;        // output row whose window [yo - ry, yo + ry] is now complete
+        const int yo = p - lead;      // output row whose window [yo - ry, yo - ry + ty.n - 1] is now complete
         if (yo >= ya) {
             float acc = 0.0f;
-            int rs = slot + 1;  // slot of walk position yo - ry = p - 2 ry  (ty.n = 2 ry + 1 slots back, wrapping)
+            int rs = slot + 1;  // slot of walk position yo - ry = p - ty.n + 1  (the oldest of the ty.n slots, wrapping)
             if (rs >= ty.n) rs -= ty.n;
             for (int s = 0; s < ty.n; ++s) {
                 acc = fmaf(ring[rs * 64 + lane], ty.w[s], acc);
@@ -215,7 +218,8 @@ __global__ __launch_bounds__(256) void k_gauss_z(const float* __restrict__ src, 
     int slot = 0;
     constexpr int PF = 8;  // planes requested ahead of the walk (one load per step left the pass latency-bound at 2 TB/s)
     float in[PF];
-    const int p_end = zb + rz;
+    const int lead = tz.n - 1 - rz;  // as in k_gauss_xy: rz for odd tap counts, rz - 1 for even ones
+    const int p_end = zb + lead;
     auto fetch = [&](int p) { return src[col + (size_t)min(max(p, 0), nz - 1) * pstride]; };
 #pragma unroll
     for (int u = 0; u < PF; ++u) in[u] = fetch(za - rz + u);  // (clamped: harmless beyond the end)
@@ -226,7 +230,7 @@ __global__ __launch_bounds__(256) void k_gauss_z(const float* __restrict__ src, 
             if (p >= p_end) break;
             ring[slot * 256] = in[u];
             in[u] = fetch(p + PF);
-            const int zo = p - rz;
+            const int zo = p - lead;
             if (zo >= za) {
                 float acc = 0.0f;
                 int rs = slot + 1;
@@ -521,6 +525,38 @@ bool gauss3d_fuses(int nx, const int* k) {
     return (nx % 4) == 0 && (k[0] & 1) && (k[1] & 1) && (k[2] & 1) && fused_lds_bytes(k) <= kFusedLdsMax && patch <= GF_NPRE * (GF_TX / 4) * GF_TY;
 }
 
+// The kernels that filter an nx x ny x nz volume with tap counts k: the ONE place where the route is decided (gauss3d_to launches
+// from this, mi_gauss3d_route reports it, so a test can assert the route it means to cover).  Pure host arithmetic.
+constexpr bool gauss_win_built(int n) { return n >= 3 && n <= 25 && (n & 1); }  // k_gauss_xy_win<N> / k_gauss_z_win<N> exist for these N
+struct GaussRoute {
+    int kind;      // MI_GAUSS_ROUTE_WAVE, _FUSED or _TWO_PASS
+    int wx;        // wave: tiles of 64 wx columns
+    bool xy_win;   // two-pass: k_gauss_xy_win (registers) instead of the k_gauss_xy ring
+    bool z_win;    // two-pass: k_gauss_z_win instead of the k_gauss_z ring
+};
+enum { MI_GAUSS_ROUTE_WAVE = 1, MI_GAUSS_ROUTE_FUSED = 2, MI_GAUSS_ROUTE_TWO_PASS = 3 };
+GaussRoute gauss3d_route(int nx, int ny, int nz, const int* k) {
+    (void)nz;
+    GaussRoute r{MI_GAUSS_ROUTE_TWO_PASS, 1, false, false};
+    if (gauss3d_fuses(nx, k)) {
+        // the filters of the RL loop's regularisation step (patch offsets inside a plane are 32-bit)
+        const bool wave = k[0] <= 2 * GW_MAXR + 1 && k[1] <= 2 * GW_MAXR + 1 && (k[2] == 3 || k[2] == 5 || k[2] == 7) &&
+                          (size_t)ny * nx < ((size_t)1 << 31);
+        r.kind = wave ? MI_GAUSS_ROUTE_WAVE : MI_GAUSS_ROUTE_FUSED;
+        if (wave) r.wx = nx >= 512 ? 2 : 1;   // tiles of 128 columns where a row has enough of them
+        return r;
+    }
+    r.xy_win = k[0] == k[1] && gauss_win_built(k[0]);   // the usual odd sizes, equal in x and y; others take the LDS ring
+    r.z_win = gauss_win_built(k[2]);
+    return r;
+}
+// the code of mi_gauss3d_route (include/mi_lsdeconv.h)
+int gauss3d_route_code(const GaussRoute& r) {
+    if (r.kind == MI_GAUSS_ROUTE_WAVE) return r.wx == 2 ? 2 : 1;
+    if (r.kind == MI_GAUSS_ROUTE_FUSED) return 3;
+    return 4 + (r.xy_win ? 1 : 0) + (r.z_win ? 2 : 0);
+}
+
 // out-of-place: dst = G(src), one pass when gauss3d_fuses(); *fused tells the caller which route ran (the two-pass route needs
 // dst as its intermediate and leaves the result in SRC: the reference's in-place contract)
 int gauss3d_to(hipStream_t s, float* src, float* dst, int nx, int ny, int nz, const float* sigma, const int* ksize, bool* fused) {
@@ -530,7 +566,8 @@ int gauss3d_to(hipStream_t s, float* src, float* dst, int nx, int ny, int nz, co
     int k[3];
     Taps tx, ty, tz;
     MI_TRY(resolve_taps(sigma, ksize, k, tx, ty, tz));
-    *fused = gauss3d_fuses(nx, k);
+    GaussRoute route = gauss3d_route(nx, ny, nz, k);
+    *fused = route.kind != MI_GAUSS_ROUTE_TWO_PASS;
 #ifdef MI_PROBES
     // (probe builds) the filter as a separable convolution with the replicate rule (sep3d.hip: k_sep3d_acc).  Bit-identical to the
     // kernels below; measured on a C3-sized volume incl. the copy back (profiles/gauss_time.py): 5 taps 8.6 against 8.4 ms,
@@ -550,10 +587,10 @@ int gauss3d_to(hipStream_t s, float* src, float* dst, int nx, int ny, int nz, co
     }
 #endif
     static const bool no_wave = MI_PROBE_ENV("MI_GAUSS_NO_WAVE") != nullptr;  // (probe builds: A/B against the work-group kernel)
-    if (*fused && !no_wave && k[0] <= 2 * GW_MAXR + 1 && k[1] <= 2 * GW_MAXR + 1 && (k[2] == 3 || k[2] == 5 || k[2] == 7) &&
-        (size_t)ny * nx < ((size_t)1 << 31)) {  // (patch offsets inside a plane are 32-bit)
+    if (no_wave && route.kind == MI_GAUSS_ROUTE_WAVE) route.kind = MI_GAUSS_ROUTE_FUSED;
+    if (route.kind == MI_GAUSS_ROUTE_WAVE) {
         const int zchunk = 128;
-        int wx = nx >= 512 ? 2 : 1;   // tiles of 128 columns where a row has enough of them
+        int wx = route.wx;
         if (const char* e = MI_PROBE_ENV("MI_GAUSS_WX")) wx = atoi(e) == 2 ? 2 : 1;
         const int total = ((nx + 64 * wx - 1) / (64 * wx)) * ((ny + 31) / 32) * ((nz + zchunk - 1) / zchunk);
         const dim3 grid((total + 7) / 8 * 8), block(256 * wx);
@@ -566,7 +603,7 @@ int gauss3d_to(hipStream_t s, float* src, float* dst, int nx, int ny, int nz, co
 #undef MI_GW
         return launch_check("k_gauss3d_wave");
     }
-    if (*fused) {
+    if (route.kind == MI_GAUSS_ROUTE_FUSED) {
         int GF_TX, GF_TY;
         fused_tile(&GF_TX, &GF_TY);
         int zchunk = k[2] <= 7 ? 128 : 256;
@@ -589,28 +626,29 @@ int gauss3d_to(hipStream_t s, float* src, float* dst, int nx, int ny, int nz, co
     }
     // pass 1: src -> dst (x then y, each rounded to fp32 like the reference's separate passes); pass 2: dst -> src (z)
     const dim3 gxy((nx + 63) / 64, (ny + GXY_YCHUNK - 1) / GXY_YCHUNK, (nz + GXY_WAVES - 1) / GXY_WAVES);
-    bool xy_done = false;
-    if (k[0] == k[1]) {
-#define MI_GXY(N) case N: hipLaunchKernelGGL(k_gauss_xy_win<N>, gxy, dim3(64 * GXY_WAVES), 0, s, src, dst, nx, ny, nz, tx, ty); xy_done = true; break;
-        switch (k[0]) {  // the usual odd sizes; others take the LDS ring
+    if (route.xy_win) {
+#define MI_GXY(N) case N: hipLaunchKernelGGL(k_gauss_xy_win<N>, gxy, dim3(64 * GXY_WAVES), 0, s, src, dst, nx, ny, nz, tx, ty); break;
+        switch (k[0]) {  // every N of gauss_win_built()
             MI_GXY(3) MI_GXY(5) MI_GXY(7) MI_GXY(9) MI_GXY(11) MI_GXY(13) MI_GXY(15) MI_GXY(17) MI_GXY(19) MI_GXY(21) MI_GXY(23) MI_GXY(25)
-            default: break;
+            default: return fail(MI_ERR_INVALID, "gauss3d_gpu: no k_gauss_xy_win for %d taps", k[0]);
         }
 #undef MI_GXY
-        if (xy_done) MI_TRY(launch_check("k_gauss_xy_win"));
-    }
-    if (!xy_done) {
+        MI_TRY(launch_check("k_gauss_xy_win"));
+    } else {
         const size_t lds_xy = sizeof(float) * GXY_WAVES * (size_t)(64 + 2 * (k[0] / 2) + k[1] * 64);
         hipLaunchKernelGGL(k_gauss_xy, gxy, dim3(64 * GXY_WAVES), lds_xy, s, src, dst, nx, ny, nz, tx, ty);
         MI_TRY(launch_check("k_gauss_xy"));
     }
     const dim3 gz((nx + 255) / 256, ny, (nz + GZ_ZCHUNK - 1) / GZ_ZCHUNK);
-#define MI_GZ(N) case N: hipLaunchKernelGGL(k_gauss_z_win<N>, gz, dim3(256), 0, s, dst, src, nx, ny, nz, GZ_ZCHUNK, tz); return launch_check("k_gauss_z_win");
-    switch (k[2]) {  // the usual odd sizes; others take the LDS ring
-        MI_GZ(3) MI_GZ(5) MI_GZ(7) MI_GZ(9) MI_GZ(11) MI_GZ(13) MI_GZ(15) MI_GZ(17) MI_GZ(19) MI_GZ(21) MI_GZ(23) MI_GZ(25)
-        default: break;
-    }
+    if (route.z_win) {
+#define MI_GZ(N) case N: hipLaunchKernelGGL(k_gauss_z_win<N>, gz, dim3(256), 0, s, dst, src, nx, ny, nz, GZ_ZCHUNK, tz); break;
+        switch (k[2]) {  // every N of gauss_win_built()
+            MI_GZ(3) MI_GZ(5) MI_GZ(7) MI_GZ(9) MI_GZ(11) MI_GZ(13) MI_GZ(15) MI_GZ(17) MI_GZ(19) MI_GZ(21) MI_GZ(23) MI_GZ(25)
+            default: return fail(MI_ERR_INVALID, "gauss3d_gpu: no k_gauss_z_win for %d taps", k[2]);
+        }
 #undef MI_GZ
+        return launch_check("k_gauss_z_win");
+    }
     const size_t lds_z = sizeof(float) * 256 * (size_t)k[2];
     hipLaunchKernelGGL(k_gauss_z, gz, dim3(256), lds_z, s, dst, src, nx, ny, nz, tz);
     return launch_check("k_gauss_z");
@@ -625,6 +663,15 @@ int gauss3d_async(hipStream_t s, float* vol, float* work, int nx, int ny, int nz
 }
 
 }  // namespace mi
+
+extern "C" int mi_gauss3d_route(int nx, int ny, int nz, const float* sigma, const int* ksize) {
+    MI_REQUIRE(sigma, "gauss3d_gpu: Usage: gauss3d_gpu(x, sigma [, kernel_size])");
+    MI_REQUIRE(nx > 0 && ny > 0 && nz > 0, "gauss3d_gpu: Input must be 3D.");
+    int k[3];
+    mi::Taps tx, ty, tz;
+    MI_TRY(mi::resolve_taps(sigma, ksize, k, tx, ty, tz));
+    return mi::gauss3d_route_code(mi::gauss3d_route(nx, ny, nz, k));
+}
 
 extern "C" int mi_gauss3d_inplace(int dev, void* stream, float* vol, float* work, int nx, int ny, int nz, const float* sigma,
                                   const int* ksize) {

@@ -27,7 +27,7 @@ from . import capi
 from .capi import (BOUNDARY_CIRCULAR, BOUNDARY_REPLICATE, BOUNDARY_ZERO, ENGINE_AUTO, ENGINE_DIRECT, ENGINE_FFT,
                    RlOptions, check, lib)
 
-__all__ = ["decon", "conv3d_gpu", "convn_same", "gauss3d_gpu", "edgetaper_3d", "otf_gpu", "im2single", "RLContext",
+__all__ = ["decon", "conv3d_gpu", "convn_same", "gauss3d_gpu", "gauss3d_route", "edgetaper_3d", "otf_gpu", "im2single", "RLContext",
            "make_psf_struct", "norm2", "prctile", "rescale_block", "pad_block_to_fft_shape", "unpad_block", "next_fast_len", "engine_select"]
 
 
@@ -130,16 +130,39 @@ def _vec3(v, name, cast):
     return [cast(x) for x in v]
 
 
+def _gauss_args(sigma, ksize):
+    sig = (C.c_float * 3)(*_vec3(sigma, "sigma", float))
+    ks = None
+    if ksize is not None and not (isinstance(ksize, (list, tuple, np.ndarray)) and len(ksize) == 0):
+        ks = (C.c_int * 3)(*_vec3(ksize, "kernel_size", int))
+    return sig, ks
+
+
+# mi_gauss3d_route: codes 1..7 (include/mi_lsdeconv.h)
+GAUSS_ROUTE_WAVE_WX1, GAUSS_ROUTE_WAVE_WX2, GAUSS_ROUTE_FUSED, GAUSS_ROUTE_TWO_PASS = 1, 2, 3, 4
+GAUSS_ROUTE_XY_WINDOW, GAUSS_ROUTE_Z_WINDOW = 1, 2   # added to GAUSS_ROUTE_TWO_PASS; without them the LDS-ring kernels
+
+
+def gauss3d_route(shape, sigma, ksize=None):
+    """The kernels ``gauss3d_gpu`` runs on a volume of ``shape`` (z, y, x): ``mi_gauss3d_route``'s code.  Host arithmetic only
+    (no device); sigma / ksize as for :func:`gauss3d_gpu`."""
+    if len(shape) != 3:
+        raise ValueError("Input must be 3D")
+    sig, ks = _gauss_args(sigma, ksize)
+    nx, ny, nz = _xyz(shape)
+    rc = lib().mi_gauss3d_route(nx, ny, nz, sig, ks)
+    if rc < 0:
+        check(rc)
+    return rc
+
+
 def gauss3d_gpu(x, sigma, ksize=None):
     """``x = gauss3d_gpu(x, sigma[, kernel_size])``: overwrites a CUDA tensor in place and returns it;
     sigma / ksize in reference order [x y z] (gauss3d_gpu.cu:230-261)."""
     dev = _device(x.device if isinstance(x, torch.Tensor) and x.is_cuda else None)
     t, was_np = _to_dev(x, dev, name="x")
     _check3d(t, "Input")
-    sig = (C.c_float * 3)(*_vec3(sigma, "sigma", float))
-    ks = None
-    if ksize is not None and not (isinstance(ksize, (list, tuple, np.ndarray)) and len(ksize) == 0):
-        ks = (C.c_int * 3)(*_vec3(ksize, "kernel_size", int))
+    sig, ks = _gauss_args(sigma, ksize)
     work = torch.empty_like(t)
     nx, ny, nz = _xyz(t.shape)
     check(lib().mi_gauss3d_inplace(dev.index, _stream(t), t.data_ptr(), work.data_ptr(), nx, ny, nz, sig, ks))

@@ -50,6 +50,14 @@ int mi_conv3d(int dev, void* stream, const float* img, const float* ker, float* 
 int mi_gauss3d_inplace(int dev, void* stream, float* vol, float* work, int nx, int ny, int nz,
                        const float* sigma, const int* ksize);
 
+/* Which kernels mi_gauss3d_inplace runs for this volume and filter (host arithmetic only: no device, no launch; the launch
+ * itself is decided by the same function).  Returns a code > 0, or an error < 0 for arguments mi_gauss3d_inplace refuses:
+ *   1, 2  single pass, k_gauss3d_wave<kz, WX> with WX = 1 / 2 (tiles of 64 / 128 columns)
+ *   3     single pass, k_gauss3d_fused (work-group kernel, LDS ring of planes)
+ *   4..7  two passes: 4 + 1 if x/y take the register window k_gauss_xy_win<N> (else the k_gauss_xy ring)
+ *                       + 2 if z takes k_gauss_z_win<N> (else the k_gauss_z ring) */
+int mi_gauss3d_route(int nx, int ny, int nz, const float* sigma, const int* ksize);
+
 /* bl = edgetaper_3d(bl, psf)   [LsDeconvolveMultiGPU/edgetaper_3d.m:13-44, make_taper.m:13-35]
  * In place. work = nx*ny*nz floats.  psf need not be normalised (it is divided by its sum, :14).
  * Only the border shell where the taper mask is < 1 is convolved. */

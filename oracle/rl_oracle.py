@@ -73,7 +73,8 @@ def flip3(psf: np.ndarray) -> np.ndarray:
 # --------------------------------------------------------------------------- Gaussian
 def gaussian_taps(sigma: float, ksize: int) -> np.ndarray:
     """``make_gaussian_kernel`` (gauss3d_gpu.cu:81-90): sigma is a float, sigma*sigma is
-    rounded in float, exp in double, stored as float, normalised by a double sum."""
+    rounded in float, exp in double, stored as float, normalised by a double sum.  ODD ``ksize`` only (for an even one the
+    reference's loop writes and sums ksize + 1 values: tests/gauss_util.py restates that case)."""
     s = np.float32(sigma)
     s2 = float(np.float32(s * s))
     r = ksize // 2
@@ -93,7 +94,8 @@ def gauss3d(vol: np.ndarray, sigma, ksize=None) -> np.ndarray:
     """``gauss3d_gpu(x, sigma[, ksize])``: three 1-D passes X, Y, Z with replicate
     boundary (gauss3d_gpu.cu:93-138,163-192).  ``sigma``/``ksize`` are in reference
     order ``[x, y, z]``.  Each pass accumulates in float32 like the kernel does
-    (we accumulate in float64 and round per pass: difference << 5e-5 test bound)."""
+    (we accumulate in float64 and round per pass: difference << 5e-5 test bound).  ODD sizes only, like
+    :func:`gaussian_taps`: the symmetric window of correlate1d is the reference's only then (even sizes: tests/gauss_util.py)."""
     sigma = [float(sigma)] * 3 if np.isscalar(sigma) else [float(s) for s in sigma]
     if ksize is None:
         ksize = default_ksize(sigma)
