@@ -94,6 +94,12 @@ class LightsheetInfo(C.Structure):
 ISO_MAX_STEPS = 32  # MI_ISO_MAX_STEPS
 
 
+class FftRoute(C.Structure):
+    """mi_fft_route (include/mi_lsdeconv.h)"""
+    _fields_ = [(name, C.c_int) for name in ("native", "paired", "z_kernel", "real_otf", "x_pipelined", "x_splits", "x_dynamic", "z_dynamic",
+                                              "pruned", "ty", "tc", "tl")]
+
+
 class IsodownParams(C.Structure):
     """mi_isodown_params (include/mi_isodown.h)."""
     _fields_ = [("voxel_y", C.c_double), ("voxel_x", C.c_double), ("target_voxel", C.c_double), ("alternating", C.c_int),
@@ -133,6 +139,7 @@ SIGNATURES = {
     "mi_cached_memory_bytes": (_sz, []),
     "mi_rl_fuses": (_i, [_vp]),
     "mi_rl_otf_is_real": (_i, [_vp]),
+    "mi_rl_fft_route": (_i, [_vp, C.POINTER(FftRoute)]),
     "mi_rl_sharded_begin": (_i, [_vp, _vp, _vp]),
     "mi_rl_sharded_ratio": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_int)]),
     "mi_rl_sharded_update": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(C.c_int)]),

@@ -1,45 +1,14 @@
 // Internal interface of the hand-written FFT convolution pipeline: the plan (fft_native.hip), its passes (fft_native_x.hip,
 // fft_native_yz.hip; device building blocks in fft_native_dev.h) and where its arrays lie
-// (fft_native_place.hip).
+// (fft_native_place.hip).  The grid's geometry, the plan's switches and the kernel route of every pass are pure host functions in
+// fft_native_route.h.
 #pragma once
 #include <vector>
 #include <algorithm>
 #include "conv3d_direct.h"
+#include "fft_native_route.h"
 
 namespace mi {
-
-struct NativeDims {
-    // every axis length is r3 * 2^l2 with r3 in {1, 3, 9}: x (Hx = X/2 complex points), y, z
-    int lhx2, r3x;
-    int ly2, r3;
-    int lz2, r3z;
-    int hx, ny, nz;
-    int ty, tc, tl;  // rows per x tile, columns per y tile, lines per z tile (A and B tiles each)
-    // padded grids: planes z >= z_in_hi of a convolution's input are all zero (never stored, never loaded); of its result only
-    // planes [z_out_lo, z_out_hi) and rows < y_out_hi are ever read.  Whole grid when nothing is padded.
-    int z_in_hi, z_out_lo, z_out_hi, y_out_hi;
-    int dbg;          // timing experiments only: knocks out phases of the z pass (results are then wrong)
-    int paired;       // spectra around the z pass in the pair-interleaved layout (k_y_pair, k_z_pair_pipe)
-    int zpad;         // paired layout: float4 of padding behind every row (xk, z)
-    int xrow;         // x side: complex samples from one row (z, px) to the next (ny + padding)
-    int xk0, xkn;     // paired layout: planes xk0 .. xk0 + xkn - 1 of a y / z launch (all of them, or one chunk of the blocked chain)
-    int yz0;          // forward y pass: first z plane of the launch (a z chunk of the sharded step; multiple of the planes per work-group)
-    // order of the x positions of the spectrum arrays: 0 = position p holds working index p of the x transform; 1 = the low radix-8
-    // digit rotated to the top, p = (w & 7) * (hx / 8) + (w >> 3), so that a lane of the fused x pass holds the eight points of a
-    // bottom butterfly in the registers of its global access (k_x_fused_pipe; x_rotated() picks the shapes)
-    int xrot;
-};
-
-// Padded mode: the caller's volume (extents n) sits at offset o inside the transform grid; the x passes apply the boundary
-// rule while loading (zero rule: zeros outside the data; replicate rule: clamped samples inside the window [0, w), zeros beyond)
-// and crop while storing, so no padded copy of the volume exists.
-struct PadWindow {
-    int on = 0;
-    int n[3] = {0, 0, 0};
-    int o[3] = {0, 0, 0};
-    int rep[3] = {0, 0, 0};
-    int w[3] = {0, 0, 0};
-};
 
 // Subset of the y tiles of the fused x pass: mode 0 all, 1 only the tiles [lo0, lo0+n0) and [lo1, lo1+n1), 2 all the others
 struct TileSelect {
@@ -63,6 +32,7 @@ struct NoPlacementTrial {
 struct NativeFft {
     // ---- the plan (fft_native.hip)
     NativeDims dims{};
+    NativeSwitches sw;  // the environment at the moment of init, for the plan's whole life
     DevBuf S, G, G_adj, tw;  // S: both spectrum arrays, S first
     float2* t_spec = nullptr;  // the second spectrum array T (inside S's allocation, or place.T2 when the arrays were placed by trial)
     DevBuf Gr, Gr_adj, ph;  // real form of the OTF(s) + phase tables (symmetric PSFs), see try_real_otf
@@ -76,9 +46,9 @@ struct NativeFft {
     int n_cu = 256;  // persistent kernels launch one work-group per CU
     ~NativeFft();
 
-    static bool supported(const int F[3]);
+    static bool supported(const int F[3]) { return native_supported(F); }
     // smallest supported extent >= n of axis 0 (x), 1 (y), 2 (z); 0 when there is none
-    static int good_size(int n, int axis);
+    static int good_size(int n, int axis) { return native_good_size(n, axis); }
     // buffers, tile sizes, twiddles; the OTF(s) are then built with build_otf
     int init(hipStream_t s, const int F[3], bool explicit_adjoint);
     // placed: the kernel on the circular grid (real, shape F; may alias scratch()); G (or G_adj) <- scale * FFT(placed)
@@ -92,7 +62,7 @@ struct NativeFft {
     float* scratch() { return reinterpret_cast<float*>(t_spec); }  // F floats, free between convolutions
     // after the OTFs are built: volumes handed to conv / iterate have extents n (x, y, z) and are padded on the fly
     void set_window(const int n[3], const int o[3], const int rep[3], const int k[3]);
-    bool can_fuse() const;  // consecutive convolutions may share their x passes (every padded axis follows the zero rule)
+    bool can_fuse() const { return pad_can_fuse(pw); }  // consecutive convolutions may share their x passes (every padded axis follows the zero rule)
     int conv(hipStream_t s, const float* in, bool conj_otf, float* out, int epi_kind, const ConvEpilogue& epi);
     // `conj_otf` selects the adjoint: conj(OTF), or the explicit adjoint OTF when one was given
     // n fused RL iterations on bl in place (lambda = 0, no regularisation step in between)
@@ -106,10 +76,10 @@ struct NativeFft {
     // ---- the passes (fft_native_x.hip, fft_native_yz.hip)
     int x_forward(hipStream_t s, const float* in);
     int middle(hipStream_t s, bool conj_otf);
-    int y_pass(hipStream_t s, bool inverse, bool paired, const float2* src = nullptr, float2* dst = nullptr, int xk0 = 0, int xkn = -1);
+    int y_pass(hipStream_t s, bool inverse, YRoute route, const float2* src = nullptr, float2* dst = nullptr, int xk0 = 0, int xkn = -1);
     int z_conv(hipStream_t s, bool conj_otf, const float2* src = nullptr, float2* dst = nullptr, int xk0 = 0, int xkn = -1);
     int x_inverse(hipStream_t s, float* out, int epi_kind, const ConvEpilogue& epi, bool fuse_forward, const TileSelect* part = nullptr);
-    bool z_pipelined() const;
+    bool z_pipelined() const { return z_pipe_ok(dims, sw); }
     // rows [y0, y0 + rows) of S (the x-transformed input of the next convolution): dir 0 pack into buf, 1 unpack from buf, 2 zero
     // (z0, nzc: only the planes [z0, z0 + nzc), which keep their place in the packed buffer; nzc = 0: all)
     int spectrum_rows(hipStream_t s, int y0, int rows, float2* buf, int dir, int z0 = 0, int nzc = 0);
@@ -119,12 +89,12 @@ struct NativeFft {
 
     // ---- pad window and tiles of the x passes
     PadWindow pw{};
-    bool pipe_ok() const;  // the fused x pass can run as the persistent pipelined kernel
-    bool splits() const;   // ... and a subset of its tiles (unpadded grids)
+    bool pipe_ok() const { return x_pipe_ok(dims, sw); }  // the fused x pass can run as the persistent pipelined kernel
+    bool splits() const { return !pw.on && pipe_ok(); }   // ... and a subset of its tiles (unpadded grids)
     TileSelect edge_tiles(int mode, int a0, int a1, int b0, int b1) const;
     // padded grids take the persistent x kernels too: zero rule, data at the origin, whole float4 rows and what the call site asks
     // of its pointers (`aligned`)
-    bool pad_pipe(bool aligned) const;
+    bool pad_pipe(bool aligned) const { return x_pad_pipe(dims, sw, pw, aligned); }
     // tiles of a pipelined x launch: those of the pad window (`padded`), else the caller's subset `part`, else all
     int pipe_tiles(bool padded, const TileSelect* part, TileSelect* sel, int* ntiles) const;
     // k_x_fused_pipe<.., mode> on those tiles (mode 0 fused, 1 forward only, 2 inverse only)
@@ -133,9 +103,7 @@ struct NativeFft {
     // kernels, tiles handed out by a device counter instead of a fixed stride (mi_rl_set_overlap)
     int overlap_free_cus = 0;
     bool overlap_dynamic = true;
-    bool x_dynamic = true;   // every other persistent x launch
-    DevBuf ctr;
-    bool z_dynamic = true;   // the paired z pass takes its tiles from a counter too
+    DevBuf ctr;   // (every other persistent x launch and the paired z pass take their tiles from a counter too: x_tiles_dynamic, z_tiles_dynamic)
     int ctr_slot = 0;
     int persistent_grid(hipStream_t s, int ntiles, bool overlapped, unsigned* grid, int** ctr_out);
 

@@ -33,113 +33,60 @@
 
 namespace mi {
 
-// An axis length n = r3 * 2^l2 with r3 in {1, 3, 9}: powers of two from 8 to 4096, or 3 * / 9 * (32 .. 512).  (A radix-3/9
-// factor matters most on y, the axis the slab driver shards, where slab + halos is rarely a power of two; on x and z it
-// keeps zero-padded deconFFT shapes close to the 7-smooth ones.)
-static bool split_axis(int n, int* r3, int* l2, bool five = false) {
-    for (int r : {1, 3, 5, 9}) {
-        if (n % r || (r == 5 && !five)) continue;
-        const int m = n / r;
-        if (!is_pow2(m)) continue;
-        const int l = ilog2(m);
-        if (r == 1 ? (l >= 3 && l <= 12) : (l >= 5 && l <= (r == 5 ? 8 : 9))) { *r3 = r; *l2 = l; return true; }
-    }
-    return false;
+// The switches of a plan, from the environment of this moment: the only place of the pipeline that reads it (names, defaults and
+// clamping of every switch are the public ones of DESIGN section 5; MI_PROBE_ENV: the probe build's experiments, absent from the product)
+static NativeSwitches read_switches() {
+    NativeSwitches w;
+    const auto set = [](const char* name) { return std::getenv(name) != nullptr; };
+    const auto mb = [](const char* name, size_t dflt) {
+        const char* e = std::getenv(name);
+        return e ? (size_t)std::max(0LL, atoll(e)) << 20 : dflt;
+    };
+    w.no_pair = set("MI_FFT_NO_PAIR");
+    w.no_pipe = set("MI_FFT_NO_PIPE");
+    w.no_xpipe = set("MI_FFT_NO_XPIPE");
+    w.no_prune = set("MI_FFT_NO_PRUNE");
+    w.complex_otf = set("MI_FFT_COMPLEX_OTF");
+    if (const char* e = std::getenv("MI_X_DYN")) w.x_dyn = atoi(e) != 0;
+    if (const char* e = std::getenv("MI_Z_DYN")) w.z_dyn = atoi(e) != 0;
+    w.place_min = mb("MI_FFT_PLACE_MIN_MB", w.place_min);
+    w.alt_min = mb("MI_FFT_PLACE_ALT_MIN_MB", w.alt_min);
+    if (const char* e = std::getenv("MI_FFT_PLACE_CANDIDATES")) w.place_candidates = std::max(1, std::min(8, atoi(e)));
+    w.place_log = set("MI_FFT_PLACE_LOG");
+    if (const char* e = MI_PROBE_ENV("MI_FFT_ZDBG")) w.dbg = atoi(e);  // phase knock-out for timing experiments
+    if (const char* e = MI_PROBE_ENV("MI_FFT_TY")) w.ty = std::max(2, atoi(e));  // tuning overrides
+    if (const char* e = MI_PROBE_ENV("MI_FFT_TC")) w.tc = std::max(1, atoi(e));
+    if (const char* e = MI_PROBE_ENV("MI_FFT_TL")) w.tl = std::max(2, atoi(e));
+    if (const char* e = MI_PROBE_ENV("MI_FFT_ZPAD")) w.zpad = std::max(0, atoi(e));
+    if (const char* e = MI_PROBE_ENV("MI_FFT_XPAD")) w.xpad = std::max(0, atoi(e));
+    if (const char* e = MI_PROBE_ENV("MI_X_FREE_CUS")) w.x_free_cus = std::max(0, atoi(e));
+    if (const char* e = MI_PROBE_ENV("MI_FFT_STGAP")) w.stgap = (size_t)atoll(e) & ~(size_t)127;
+    return w;
 }
 
-static const int kMaxZ = 2304;  // 2 * TL >= 4 rows of the z pass must fit the LDS tile
-static const int kMaxLen = 9 << 9;  // the longest length of split_axis
-
-bool NativeFft::supported(const int F[3]) {
-    // x: real length 2 * Hx, the transform runs on Hx complex points
-    int r3, l2;
-    return F[0] % 2 == 0 && split_axis(F[0] / 2, &r3, &l2) && split_axis(F[1], &r3, &l2, true) && split_axis(F[2], &r3, &l2) && F[2] <= kMaxZ;
-}
-
-int NativeFft::good_size(int n, int axis) {
-    // (the searches end at the longest length split_axis takes, 9 * 2^9: beyond it there is no extent, and the answer is 0)
-    int r3, l2;
-    if (axis == 0) {
-        for (int h = n < 16 ? 8 : (n + 1) / 2; h <= kMaxLen; ++h)
-            if (split_axis(h, &r3, &l2)) return 2 * h;
-        return 0;
-    }
-    for (int m = n < 8 ? 8 : n; m <= (axis == 2 ? kMaxZ : kMaxLen); ++m)
-        if (split_axis(m, &r3, &l2, axis == 1)) return m;
-    return 0;
-}
-
+// resolve the switches, the geometry (plan_geometry), allocate, fill the tables, place the arrays
 int NativeFft::init(hipStream_t s, const int F[3], bool explicit_adjoint) {
+    sw = read_switches();
     MI_REQUIRE(supported(F), "native FFT: unsupported shape %d x %d x %d", F[0], F[1], F[2]);
-    const int Hx = F[0] / 2;
-    split_axis(Hx, &dims.r3x, &dims.lhx2);
-    split_axis(F[1], &dims.r3, &dims.ly2, true);  // (the y axis also takes 5 * 2^a: 320 rows of a slab rank instead of 384)
-    split_axis(F[2], &dims.r3z, &dims.lz2);
-    dims.hx = Hx;
-    dims.xrot = x_rotated(dims.lhx2, dims.r3x) ? 1 : 0;
-    dims.ny = F[1];
-    dims.nz = F[2];
-    dims.ty = std::min(x_tile_rows(Hx), F[1]);
-    dims.tc = y_tile_cols(F[1]);
-    dims.tl = std::min(z_tile_lines(F[2]), F[1]);
-    dims.z_in_hi = F[2];
-    dims.z_out_lo = 0;
-    dims.z_out_hi = F[2];
-    dims.y_out_hi = F[1];
-    dims.xk0 = 0;
-    dims.xkn = Hx / 2 + 1;
-    dims.yz0 = 0;
-    dims.dbg = 0;
-    if (const char* e = MI_PROBE_ENV("MI_FFT_ZDBG")) dims.dbg = atoi(e);  // phase knock-out for timing experiments
-    // tuning overrides (experiments only): MI_FFT_TY / MI_FFT_TC / MI_FFT_TL
-    if (const char* e = MI_PROBE_ENV("MI_FFT_TY")) dims.ty = std::max(2, std::min(atoi(e), F[1]));
-    if (const char* e = MI_PROBE_ENV("MI_FFT_TC")) dims.tc = std::max(1, atoi(e));
-    if (const char* e = MI_PROBE_ENV("MI_FFT_TL")) dims.tl = std::max(2, std::min(atoi(e), F[1]));
-    while ((size_t)F[2] * Hx % dims.tc) dims.tc >>= 1;
-    // tiles are whole float4 groups of rows / lines and must divide y; z tiles of TL positions must map onto aligned
-    // mirror blocks, which holds for TL <= 2^ly2 (positions inside one power-of-two sub-block mirror inside one)
-    MI_REQUIRE(dims.ty >= 2 && dims.ty % 2 == 0 && F[1] % dims.ty == 0, "native FFT: x tile of %d rows does not divide y = %d", dims.ty, F[1]);
-    MI_REQUIRE(dims.tl >= 2 && is_pow2(dims.tl) && dims.tl <= (1 << dims.ly2), "native FFT: z tile of %d lines does not fit y = %d", dims.tl, F[1]);
-    MI_REQUIRE(lds_bytes(dims.ty, Hx) <= 160 * 1024 && lds_bytes(dims.tc, F[1]) <= 160 * 1024 &&
-                   lds_bytes(2 * dims.tl, F[2]) <= 160 * 1024,
-               "native FFT: transform too long for LDS");
-    // pair-interleaved z-side layout (k_y_pair / k_z_pair_pipe): z a power of two the paired z pass takes, whole blocks of
-    // kPairLines lines, an even number of columns per y tile; MI_FFT_NO_PAIR=1 keeps the plain layout (A/B measurements)
-    const bool z_pairs = dims.r3z == 1 ? (dims.lz2 >= 6 && dims.lz2 <= 10)
-                         : dims.r3z == 3 ? (dims.lz2 >= 6 && dims.lz2 <= 8) : (dims.r3z == 9 && dims.lz2 >= 6 && dims.lz2 <= 7);
-    dims.paired = z_pairs && F[1] % (2 * kPairLines) == 0 && dims.tc >= 2 && dims.tc % 2 == 0 &&
-                  F[2] % (dims.tc / 2) == 0 && dims.dbg == 0 && std::getenv("MI_FFT_NO_PAIR") == nullptr &&
-                  std::getenv("MI_FFT_NO_PIPE") == nullptr && MI_PROBE_ENV("MI_FFT_TL") == nullptr;
-    n_cplx = (size_t)Hx * F[1] * F[2];
-    // (the two planes that are their own mirror partners are stored twice in the paired layout)
-    // Rows an exact power of two apart camp on few HBM channels: behind every row of the x side ([z][px][.]) and of the paired z
-    // side ([xk][z][.]) that is at least 8 KB long lie 4 KB + 128 B of padding.  C3 (profiles/zpad_probe.py): z pass 4.75 -> 4.2 ms
-    // with any odd multiple of 128 B behind the z rows (64-byte offsets break the 128-byte lines: 6.2 ms); with 4 KB + 128 B
-    // on both sides the y passes drop from 3.2-3.35 to 2.85-3.35 ms and the x pass from 5.1 / 6.0-7.2 to 4.75 / 5.7-6.8 ms.
-    const int pad_x = (size_t)F[1] * sizeof(float2) >= kPadRowBytes ? kRowPadBytes : 0;
-    const int pad_z = (size_t)F[1] * 2 * sizeof(float2) >= kPadRowBytes ? kRowPadBytes : 0;
-    dims.zpad = dims.paired ? pad_z / 16 : 0;
-    dims.xrow = F[1] + pad_x / 8;
-    if (const char* e = MI_PROBE_ENV("MI_FFT_ZPAD")) dims.zpad = dims.paired ? std::max(0, atoi(e)) : 0;   // float4 per row
-    if (const char* e = MI_PROBE_ENV("MI_FFT_XPAD")) dims.xrow = F[1] + 2 * std::max(0, atoi(e));          // float4 per row
-    const size_t n_x = (size_t)Hx * F[2] * dims.xrow;
-    const size_t n_buf = std::max(n_x, dims.paired ? (size_t)(Hx / 2 + 1) * F[2] * 2 * (size_t)(F[1] + dims.zpad) : n_cplx);
-    // one allocation for both arrays: their distance -- which decides how the strided streams of a pass that reads one and
-    // writes the other fall onto the HBM channels -- is then the same in every context instead of whatever the driver returns
+    NativeSizes sz{};
+    const int miss = plan_geometry(F, sw, &dims, &sz);
+    MI_REQUIRE(miss != 1, "native FFT: x tile of %d rows does not divide y = %d", dims.ty, F[1]);
+    MI_REQUIRE(miss != 2, "native FFT: z tile of %d lines does not fit y = %d", dims.tl, F[1]);
+    MI_REQUIRE(miss == 0, "native FFT: transform too long for LDS");
+    const int Hx = dims.hx;
+    const size_t n_buf = sz.n_buf, gap = sw.stgap;
+    n_cplx = sz.n_cplx;
+    // one allocation for both arrays, NativeSwitches::stgap apart
     // (measuring the passes for six distances at plan time did not pay: in a process where the y passes run in their slow mode
     // they do so for every distance tried)
-    size_t gap = kSpecGapBytes;
-    if (const char* e = MI_PROBE_ENV("MI_FFT_STGAP")) gap = (size_t)atoll(e) & ~(size_t)127;
     MI_TRY(S.alloc(sizeof(float2) * 2 * n_buf + gap));
     t_spec = S.as<float2>() + n_buf + gap / sizeof(float2);
     spec_bytes = sizeof(float2) * n_buf;
     MI_TRY(G.alloc(sizeof(float4) * (size_t)(Hx / 2 + 1) * F[1] * F[2]));
-    // twiddle tables exp(-2 pi i e / N) in double on the host, per axis: e < sub/2 for the power-of-two sub-transform
-    // (sub = 2^l2), followed by the full circle e < n of the radix-3/9 stage when the axis has one
+    // twiddle tables exp(-2 pi i e / N) in double on the host, per axis (NativeSizes)
     const int lens[3] = {Hx, F[1], F[2]};
     const int subs[3] = {1 << dims.lhx2, 1 << dims.ly2, 1 << dims.lz2};
-    size_t off = 0, offs[3];
-    for (int a = 0; a < 3; ++a) { offs[a] = off; off += (size_t)std::max(1, subs[a] / 2) + (lens[a] != subs[a] ? (size_t)lens[a] : 0); }
+    const size_t off = sz.tw_total, *offs = sz.tw_at;
     std::vector<float2> h(off);
     const double two_pi = 6.283185307179586476925286766559;
     for (int a = 0; a < 3; ++a) {
@@ -166,9 +113,7 @@ int NativeFft::init(hipStream_t s, const int F[3], bool explicit_adjoint) {
     // large arrays are placed by trial (fft_native_place.hip): MI_FFT_PLACE_MIN_MB (6144, both together) and more -- smaller plans are
     // not tried: decwrap creates its block plans, 3-4 GB each, on several workers per device while others compute, and every released
     // candidate is a device-wide synchronisation (slab.SlabRL lowers the limit for its rank, which has its device to itself)
-    size_t place_min = (size_t)6 << 30;
-    if (const char* e = std::getenv("MI_FFT_PLACE_MIN_MB")) place_min = (size_t)std::max(0LL, atoll(e)) << 20;
-    if (S.bytes >= place_min && !NoPlacementTrial::active()) MI_TRY(place_by_trial(s, gap));
+    if (S.bytes >= sw.place_min && !NoPlacementTrial::active()) MI_TRY(place_by_trial(s, gap));
     return MI_OK;
 }
 
@@ -188,7 +133,7 @@ void NativeFft::set_window(const int n[3], const int o[3], const int rep[3], con
         pw.w[a] = n[a] + k[a] - 1;
     }
     // what the padding leaves to prune (MI_FFT_NO_PRUNE=1 keeps the full passes, for A/B measurements)
-    if (std::getenv("MI_FFT_NO_PRUNE") != nullptr) return;
+    if (sw.no_prune) return;
     const int in_hi = rep[2] ? pw.w[2] : o[2] + n[2];
     dims.z_in_hi = std::min(in_hi, dims.nz);
     dims.z_out_lo = o[2];
@@ -197,13 +142,11 @@ void NativeFft::set_window(const int n[3], const int o[3], const int rep[3], con
     dims.y_out_hi = std::min(yh, dims.ny);
 }
 
-bool NativeFft::can_fuse() const { return !pw.on || !(pw.rep[0] || pw.rep[1] || pw.rep[2]); }
-
 // P2, P3, P4: S[z][px][py] -> T[z][px][py] (x still transformed), multiplied by the OTF or its conjugate
 int NativeFft::middle(hipStream_t s, bool conj_otf) {
-    MI_TRY(y_pass(s, false, dims.paired != 0));
+    MI_TRY(y_pass(s, false, y_route(dims)));
     MI_TRY(z_conv(s, conj_otf));
-    return y_pass(s, true, dims.paired != 0);
+    return y_pass(s, true, y_route(dims));
 }
 
 NativeFft::~NativeFft() {

@@ -15,9 +15,6 @@ namespace {
 #ifndef MI_FFT_UNROLL
 #define MI_FFT_UNROLL 4
 #endif
-constexpr int kThreadsXZ = 1024;  // strided passes: one ~140-KB work-group of 16 waves per CU
-constexpr int kWavesXZ = 4;       // waves per SIMD the register budget is sized for (128 VGPRs)
-constexpr int kThreadsY = 512;    // contiguous pass: two work-groups per CU
 #ifndef MI_YCUT
 #define MI_YCUT 1
 #endif
@@ -56,8 +53,6 @@ __device__ __forceinline__ int rmask(int row, int hp) {
     const int s = hp == 8 ? 1 : hp == 4 ? 2 : hp == 2 ? 3 : 0;
     return (rp << s) ^ ((rp & 1) << 4);
 }
-// rows start on a multiple of 32 slots, so that only the masks decide the banks
-__host__ __device__ constexpr int row_pitch(int n) { return (n + 31) & ~31; }
 
 __device__ __forceinline__ int launder(int x) {
     asm volatile("" : "+v"(x));
@@ -128,8 +123,6 @@ __device__ __forceinline__ int mirror_pos(int p, int n, int l2, int r3) {
 // x positions (NativeDims::xrot): the index w the x transform works with ("working index": w = freq2pos(xk) of the rule above) sits
 // at position w, or -- rotated order -- at (w & 7) * (Hx / 8) + (w >> 3).  The eight points 8a .. 8a + 7 of a bottom radix-8
 // butterfly then lie Hx / 8 positions apart, which is the stride of the eight items a lane of k_x_fused_pipe loads and stores.
-// The shapes that take the rotated order: power-of-two rows whose tile is eight float4 per lane with that stride.
-__host__ __device__ constexpr bool x_rotated(int lhx2, int r3) { return r3 == 1 && (lhx2 == 10 || lhx2 == 11); }
 // (branch-free: digit width r = 3 and shift s = lhx2 - 3 when rotated, both 0 otherwise -- then both maps are the identity)
 __device__ __forceinline__ int x_work2pos(int w, const NativeDims& d) {
     const int r = 3 * d.xrot, s = d.xrot * (d.lhx2 - 3);
@@ -170,46 +163,6 @@ __device__ __forceinline__ constexpr float s16(int k) {
 }
 
 // ------------------------------------------------------------------------------------------------ super-stage chains
-// The log2(N) radix-2 stages of a transform are cut, bottom-up, into super-stages of 3 stages (8 points per lane in
-// registers; a remainder of 4 becomes 2 + 2 -- one stage of 16 points for 1024-point transforms --, a remainder of 1 or 2 sits at the top): seg_r(logn, s) is the length of the
-// super-stage that starts at stage s.  The same cut serves both directions (forward walks it top-down, inverse bottom-up),
-// and all its (S_LO, LR) pairs below stage 5 are among the conflict-free patterns of the swizzle.
-__host__ __device__ constexpr int seg_r(int logn, int s, int cut = 0) {
-    const int rem = logn - s;
-    if (logn == 4) return s == 0 ? 3 : 1;
-    // 1024 points as 8 x 8 x 16 -- three LDS round trips instead of the four of 8 x 8 x 4 x 4 (round 4; C3: ratio launch of the x
-    // pass 5.07 -> 4.76 ms, the z pass of 1024-point lines 6.15 -> 5.71 ms, the y passes of C2 0.426 -> 0.416 ms).  The sixteen-point
-    // butterfly reads its fifteen twiddles where it uses them (butterflies): held together they spilled.
-    if (logn == 10 && rem == 4) return 4;
-    // cut 1 (the y kernels: 512 threads, 256 registers to spend): 2048 points as 16 x 16 x 8 and 4096 as 16 x 16 x 16 -- three round
-    // trips instead of four (round 5; C3: y passes 3.06 / 3.10 -> 2.99 / 2.93 ms).  The x kernels keep 8 x 8 x 8 x 4 for 2048 points:
-    // at their 128 registers the sixteen-point butterflies cost more than the round trip (C4-shaped rank: x pass 7.0 / 7.9 ms
-    // against 7.7 / 8.6 with 16 x 16 x 8 and 9.5 / 10.6 with 8 x 16 x 16, profiles/r05_fft_cut_2048.txt).
-    if (cut == 1 && logn == 11) return s < 8 ? 4 : 3;
-    if (cut == 1 && logn == 12) return 4;
-    return rem >= 5 ? 3 : rem == 4 ? 2 : rem;  // rem in {1, 2, 3}: all of it
-}
-// start of the super-stage that ends at stage `top` (exclusive)
-__host__ __device__ constexpr int seg_below(int logn, int top, int cut = 0) {
-    int s = 0;
-    while (s + seg_r(logn, s, cut) < top) s += seg_r(logn, s, cut);
-    return s;
-}
-// LDS twiddle tables: every super-stage with S_LO > 0 owns a packed table of 2^S_LO entries, exp(-2 pi i m / 2^(S_LO+LR))
-// (stride-1 look-ups: no bank conflicts, and no vector-memory loads inside the FFT phases -- those would drain the prefetch
-// queue, vmcnt being in order); the tables lie one after the other, bottom-up.  tw_off: offset of the table of stage s.
-// Powers kept per lane-twiddle index: all R - 1 of them while the table stays small (stage <= 6), else only the first (the
-// others are derived by multiplications).
-__host__ __device__ constexpr int tw_powers(int s, int r) { return s <= 6 ? (1 << r) - 1 : 1; }
-__host__ __device__ constexpr int tw_off(int logn, int s, int cut = 0) {
-    int off = 0, t = 0;
-    while (t < s) {
-        if (t > 0) off += tw_powers(t, seg_r(logn, t, cut)) << t;
-        t += seg_r(logn, t, cut);
-    }
-    return off;
-}
-__host__ __device__ constexpr int chain_entries(int logn, int cut = 0) { return tw_off(logn, logn, cut); }
 // gather the tables from the global table tw[e] = exp(-2 pi i e / 2^LOGN), e < 2^(LOGN-1): entry [p - 1][m] of the super-stage
 // at S is exp(-2 pi i m p / 2^(S+r)), the p-th power of the lane twiddle of group element m
 template <int LOGN, int NT, int S = 0, int CUT = 0>
@@ -243,40 +196,6 @@ struct TwLds {
         }
     }
 };
-// twiddle entries in LDS for an axis of length n = r3 * 2^l2
-__host__ __device__ constexpr int axis_tw_entries(int n) {
-    int r3 = 1, l2 = 0;
-    while (n % 3 == 0) { n /= 3; r3 *= 3; }
-    while (n % 5 == 0) { n /= 5; r3 *= 5; }
-    while ((1 << l2) < n) ++l2;
-    return chain_entries(l2) + (r3 > 1 ? (1 << l2) : 0);
-}
-#ifndef MI_Y_TILE_CAP
-#define MI_Y_TILE_CAP 16
-#endif
-constexpr int kLdsOneWg = 156 * 1024;  // one work-group per CU (160 KB LDS)
-constexpr int kLdsTwoWg = 78 * 1024;   // two work-groups per CU
-constexpr size_t kSpecGapBytes = 4224;  // bytes between the end of S and the start of T (NativeFft::init)
-constexpr int kRowPadBytes = 4224;     // padding behind the rows of the spectrum arrays ...
-constexpr size_t kPadRowBytes = 8192;  // ... that are at least this long (NativeFft::init)
-constexpr int kPairLines = 8;          // lines per block of the pair-interleaved z-side layout (8 A + 8 B lines = 128 bytes)
-// rows of an x tile / line pairs of a z tile: 16 (full 128-B lines in the transposed layouts) while tile + tables fit one
-// work-group per CU; columns of a y tile: two work-groups per CU
-__host__ __device__ constexpr int x_tile_rows(int hx) {
-    int rows = 16;
-    while (rows > 2 && 8 * (rows * row_pitch(hx) + axis_tw_entries(hx)) > kLdsOneWg) rows >>= 1;
-    return rows;
-}
-__host__ __device__ constexpr int z_tile_lines(int nz) {
-    int tl = 16;
-    while (tl > 2 && 8 * (2 * tl * row_pitch(nz) + axis_tw_entries(nz)) > kLdsOneWg) tl >>= 1;
-    return tl;
-}
-__host__ __device__ constexpr int y_tile_cols(int ny) {
-    int tc = MI_Y_TILE_CAP;
-    while (tc > 1 && 8 * (tc * row_pitch(ny) + axis_tw_entries(ny)) > kLdsTwoWg) tc >>= 1;
-    return tc;
-}
 
 // Sequences of a tile: `batch` = rows * R3 power-of-two sub-transforms of length 2^LOGN; sequence b = row b / R3, sub-block
 // b % R3 (elements [sub << LOGN, (sub + 1) << LOGN) of the row).  PRIV: the rows are dealt to the waves (row r belongs to
@@ -587,13 +506,6 @@ __device__ __forceinline__ void radix3_stage(float2* tile, int cols, int pitch, 
 __device__ __forceinline__ int cell(int row, int pitch, int hp, int e) { return row * pitch + (phys(e) ^ rmask(row, hp)); }
 
 // ------------------------------------------------------------------------------------------------ host side of the units
-bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-
-// LDS of an axis kernel: the tile, then the twiddle tables (both chains and the radix-3/9 table: what the fused kernels of
-// the axis use, an upper bound for the others; see TwLds)
-size_t lds_bytes(int rows, int n) { return sizeof(float2) * ((size_t)rows * row_pitch(n) + axis_tw_entries(n)); }
-
 template <class K, class... Args>
 int launch_lds(K kernel, unsigned grid, int threads, size_t lds, hipStream_t s, const char* name, Args... args) {
     if (lds > 64 * 1024)
@@ -604,15 +516,9 @@ int launch_lds(K kernel, unsigned grid, int threads, size_t lds, hipStream_t s, 
 
 // ---- launch dispatch: the kernels are templated on (log2 of the power-of-two part, radix-3/9 factor) of their axis;
 // key = l2 * 16 + r3
-#define MI_AXIS_CASES(M) M(3, 1) M(4, 1) M(5, 1) M(6, 1) M(7, 1) M(8, 1) M(9, 1) M(10, 1) M(11, 1) M(12, 1) \
-    M(5, 3) M(6, 3) M(7, 3) M(8, 3) M(9, 3) M(5, 9) M(6, 9) M(7, 9) M(8, 9) M(9, 9)
-// y: also 5 * 2^a (only the y kernels are built for it)
-#define MI_Y_CASES(M) MI_AXIS_CASES(M) M(5, 5) M(6, 5) M(7, 5) M(8, 5)
-// z: lengths up to kMaxZ
-#define MI_Z_CASES(M) M(3, 1) M(4, 1) M(5, 1) M(6, 1) M(7, 1) M(8, 1) M(9, 1) M(10, 1) M(11, 1) \
-    M(5, 3) M(6, 3) M(7, 3) M(8, 3) M(9, 3) M(5, 9) M(6, 9) M(7, 9) M(8, 9)
-// One switch per case list: f -- a generic lambda that names the kernel -- is called with the (LG, R) of the axis as
-// std::integral_constant arguments and its result returned; a length outside the list is the "unsupported" failure.
+// One switch per case list of the length table (fft_native_route.h): f -- a generic lambda that names the kernel -- is called with
+// the (LG, R) of the axis as std::integral_constant arguments and its result returned; a length outside the list is the
+// "unsupported" failure.
 template <int V>
 using Int = std::integral_constant<int, V>;
 #define MI_CASE_CALL(LG, R) case LG * 16 + R: return f(Int<LG>{}, Int<R>{});
@@ -624,9 +530,13 @@ template <class F>
 int y_case(const NativeDims& d, F&& f) {
     switch (d.ly2 * 16 + d.r3) { MI_Y_CASES(MI_CASE_CALL) default: return fail(MI_ERR_UNSUPPORTED, "native FFT: y length %d", d.ny); }
 }
+#undef MI_CASE_CALL
+// (z: no kernel is built for the lengths beyond kMaxZ)
+#define MI_CASE_CALL(LG, R) case LG * 16 + R: if constexpr (axis_takes(2, LG, R)) return f(Int<LG>{}, Int<R>{}); else break;
 template <class F>
 int z_case(const NativeDims& d, F&& f) {
-    switch (d.lz2 * 16 + d.r3z) { MI_Z_CASES(MI_CASE_CALL) default: return fail(MI_ERR_UNSUPPORTED, "native FFT: z length %d", d.nz); }
+    switch (d.lz2 * 16 + d.r3z) { MI_AXIS_CASES(MI_CASE_CALL) default: break; }
+    return fail(MI_ERR_UNSUPPORTED, "native FFT: z length %d", d.nz);
 }
 #undef MI_CASE_CALL
 

@@ -30,8 +30,7 @@ bool NoPlacementTrial::active() { return tl_no_placement_trial != 0; }
 int NativeFft::place_by_trial(hipStream_t s, size_t gap) {
     const int Hx = dims.hx;
     const size_t n_buf = spec_bytes / sizeof(float2);
-    int tries = 6;
-    if (const char* e = std::getenv("MI_FFT_PLACE_CANDIDATES")) tries = std::max(1, std::min(8, atoi(e)));
+    int tries = sw.place_candidates;
     // one trial at a time per device (plans created concurrently -- decwrap's workers with a large --block-size-max -- would each
     // hold their candidates and push each other out of memory); what the pool keeps cached goes back to the driver first: the
     // candidates are allocated behind the pool's back and get none of its trim-on-failure
@@ -85,7 +84,7 @@ int NativeFft::place_by_trial(hipStream_t s, size_t gap) {
             S.p = cand[i];
             t_spec = static_cast<float2*>(cand[j]);
             float ty = 0.0f, tx = 0.0f;
-            timed([&] { return y_pass(s, false, dims.paired != 0); }, &ty);
+            timed([&] { return y_pass(s, false, y_route(dims)); }, &ty);
             if (xtmp) {
                 ConvEpilogue ep;
                 ep.a = static_cast<const float*>(xtmp);
@@ -100,9 +99,7 @@ int NativeFft::place_by_trial(hipStream_t s, size_t gap) {
     // a second buffer for S stays until the first call that brings the caller's volume: the update launch is slow when S
     // shares a region with THAT volume, which nothing here can know (NativeFft::iterate settles it: settle_s)
     int bk = -1;
-    size_t alt_min = (size_t)8 << 30;   // (MI_FFT_PLACE_ALT_MIN_MB: the smallest array that keeps a second buffer for S)
-    if (const char* e = std::getenv("MI_FFT_PLACE_ALT_MIN_MB")) alt_min = (size_t)std::max(0LL, atoll(e)) << 20;
-    if (rc == MI_OK && bi >= 0 && half >= alt_min)
+    if (rc == MI_OK && bi >= 0 && half >= sw.alt_min)   // (MI_FFT_PLACE_ALT_MIN_MB: the smallest array that keeps a second buffer for S)
         for (int k = 0; k < K; ++k)
             if (k != bi && k != bj && tyv[(size_t)k * K + bj] <= 1.03f * tyv[(size_t)bi * K + bj] + 0.02f &&
                 (bk < 0 || tyv[(size_t)k * K + bj] < tyv[(size_t)bk * K + bj]))
@@ -124,7 +121,7 @@ int NativeFft::place_by_trial(hipStream_t s, size_t gap) {
         t_spec = place.T2.as<float2>();
         place.placement_ms = ms;
         place.placement_kept = kept_idx;   // (index in the list of ordered pairs (i, j), i != j, i slowest)
-        if (std::getenv("MI_FFT_PLACE_LOG")) {   // (diagnostics on stderr)
+        if (sw.place_log) {   // (MI_FFT_PLACE_LOG: diagnostics on stderr)
             float worst = best;
             for (float v : ms) worst = std::max(worst, v);
             std::fprintf(stderr, "native FFT: 2 x %.1f GB placed on buffers %d (S) and %d (T) of %d: 4 y + 3 update %.2f ms (pairs from %.2f to %.2f)\n",
@@ -153,7 +150,7 @@ int NativeFft::settle_decide(hipStream_t s) {
     for (auto& e : place.alt_ev) { (void)hipEventDestroy(e); e = nullptr; }
     // now S.p is the second buffer, place.S_alt.p the first
     if (he != hipSuccess || t[0] <= 1.02f * t[1]) std::swap(S.p, place.S_alt.p);
-    if (std::getenv("MI_FFT_PLACE_LOG"))
+    if (sw.place_log)
         std::fprintf(stderr, "native FFT: S settled on the %s buffer (update launch %.3f / %.3f ms with this volume)\n",
                      (he != hipSuccess || t[0] <= 1.02f * t[1]) ? "first" : "second", (double)t[0], (double)t[1]);
     (void)hipFree(place.S_alt.p);   // (waits for the device: the passes that still read it have run by then)
@@ -213,9 +210,9 @@ int NativeFft::time_pass(hipStream_t s, int which, const float* bl, int reps, fl
             case 4: return x_inverse(s, nullptr, EPI_RATIO, e, true);
             case 5: return x_inverse(s, const_cast<float*>(bl), EPI_UPDATE, e, true);
             // (blocked middle: the whole chain is quoted as pass 1, passes 2 and 3 do not exist on their own)
-            case 1: return y_pass(s, false, dims.paired != 0);
+            case 1: return y_pass(s, false, y_route(dims));
             case 2: return z_conv(s, false);
-            default: return y_pass(s, true, dims.paired != 0);
+            default: return y_pass(s, true, y_route(dims));
         }
     });
 }
@@ -230,7 +227,7 @@ int NativeFft::time_between(hipStream_t s, int which, const float2* src, float2*
     return timed_launches(s, reps, "time_between", avg_ms, [&] {
         int rc;
         if (which == 0) {
-            rc = y_pass(s, false, dims.paired != 0, src, dst);
+            rc = y_pass(s, false, y_route(dims), src, dst);
         } else if (which == 2) {   // the forward x pass reads the volume and writes S
             S.p = dst;
             rc = x_forward(s, bl);

@@ -548,12 +548,10 @@ __global__ __launch_bounds__(256) void k_spectrum_rows(float2* __restrict__ S, f
 // slowest one as the tail (C3: paired z pass 4.36 -> 3.94 ms, fused x pass 5.13 / 5.71 -> 5.06 / 5.61 ms; part 2 of a slab rank's
 // x pass at N = 8: 0.77 -> 0.66 ms; profiles/r03_overlap_probe.txt).  `overlapped`: the launch runs beside a halo exchange
 // (part 2 of a sharded step) and follows mi_rl_set_overlap: `free_cus` compute units are left to the collective's kernels.
-// MI_X_DYN=0|1 / MI_X_FREE_CUS=<k> override for every launch (A/B measurements).
+// MI_X_DYN=0|1 / MI_X_FREE_CUS=<k> (NativeSwitches) override for every launch (A/B measurements).
 int NativeFft::persistent_grid(hipStream_t s, int ntiles, bool overlapped, unsigned* grid, int** ctr_out) {
-    static const char* env_dyn = std::getenv("MI_X_DYN");
-    static const char* env_free = MI_PROBE_ENV("MI_X_FREE_CUS");
-    const bool dyn = env_dyn ? atoi(env_dyn) != 0 : (overlapped ? overlap_dynamic : x_dynamic);
-    const int free_cus = env_free ? atoi(env_free) : (overlapped ? overlap_free_cus : 0);
+    const bool dyn = x_tiles_dynamic(sw, overlapped ? overlap_dynamic : true);
+    const int free_cus = sw.x_free_cus >= 0 ? sw.x_free_cus : (overlapped ? overlap_free_cus : 0);
     const int cus = std::max(1, n_cu - std::max(0, free_cus));
     *grid = (unsigned)std::min(ntiles, cus);
     *ctr_out = nullptr;
@@ -589,13 +587,6 @@ int NativeFft::x_pipelined(hipStream_t s, int mode, const float2* T, float* out,
     });
 }
 
-// the fused x pass runs as the persistent pipelined kernel, which can also process a subset of its tiles
-bool NativeFft::pipe_ok() const {
-    static const bool no_pipe = std::getenv("MI_FFT_NO_PIPE") != nullptr;
-    return dims.dbg == 0 && !no_pipe && dims.ty == x_tile_rows(dims.hx);
-}
-bool NativeFft::splits() const { return !pw.on && pipe_ok(); }
-
 // tiles of the fused x pass that hold rows of [a0, a1) or [b0, b1) (a before b): mode 1 = only those, 2 = all the others
 TileSelect NativeFft::edge_tiles(int mode, int a0, int a1, int b0, int b1) const {
     TileSelect t{};
@@ -606,10 +597,6 @@ TileSelect NativeFft::edge_tiles(int mode, int a0, int a1, int b0, int b1) const
     t.lo1 = std::max(b0 / ty, t.lo0 + t.n0);   // overlapping ranges: the second one starts behind the first
     t.n1 = std::max((b1 + ty - 1) / ty - t.lo1, 0);
     return t;
-}
-
-bool NativeFft::pad_pipe(bool aligned) const {
-    return pw.on && can_fuse() && pipe_ok() && pw.o[0] == 0 && pw.o[1] == 0 && pw.o[2] == 0 && pw.n[0] % 4 == 0 && aligned;
 }
 
 int NativeFft::pipe_tiles(bool padded, const TileSelect* part, TileSelect* sel, int* ntiles) const {
@@ -634,14 +621,16 @@ int NativeFft::pipe_tiles(bool padded, const TileSelect* part, TileSelect* sel, 
 }
 
 int NativeFft::x_forward(hipStream_t s, const float* in) {
-    // persistent kernel with prefetch: unpadded grids, and padded ones under the conditions of the fused pass (pad_pipe)
-    const bool padded = pad_pipe(true);
-    if ((splits() || padded) && ((uintptr_t)in % 16) == 0 && std::getenv("MI_FFT_NO_XPIPE") == nullptr) {
+    // persistent kernel with prefetch: unpadded grids, and padded ones under the conditions of the fused pass (x_route)
+    XCall c;
+    c.forward = true;
+    c.aligned = ((uintptr_t)in % 16) == 0;
+    if (x_route(dims, sw, pw, c) == XRoute::pipe_forward) {
         ConvEpilogue e;
         e.a = in;
         TileSelect sel;
         int ntiles = 0;
-        MI_TRY(pipe_tiles(padded, nullptr, &sel, &ntiles));
+        MI_TRY(pipe_tiles(pw.on != 0, nullptr, &sel, &ntiles));
         return x_pipelined(s, 1, nullptr, nullptr, e, EPI_NONE, sel, ntiles);
     }
     const unsigned xtiles = (unsigned)((size_t)dims.nz * (dims.ny / dims.ty));
@@ -658,20 +647,20 @@ int NativeFft::x_inverse(hipStream_t s, float* out, int epi_kind, const ConvEpil
     MI_REQUIRE(!fuse_forward || can_fuse(), "native FFT: a replicate-padded axis cannot fuse consecutive convolutions");
     // (MI_FFT_NO_XPIPE=1 sends a whole fused pass through k_x_inverse too -- every stage in LDS, same arithmetic: the reference route
     // of tests/test_gpu_x_register_stage.py; a subset of the tiles exists only in the persistent kernel)
-    const bool whole = !(part && part->mode != 0), no_xpipe = std::getenv("MI_FFT_NO_XPIPE") != nullptr;
-    const bool aligned = ((uintptr_t)epi.a % 16) == 0 && ((uintptr_t)out % 16) == 0;
-    const bool padded = pad_pipe(aligned && whole);
-    TileSelect sel;
-    int ntiles = 0;
-    if (fuse_forward && (splits() || padded) && !(whole && no_xpipe)) {
-        MI_TRY(pipe_tiles(padded, part, &sel, &ntiles));
-        return x_pipelined(s, 0, t_spec, out, epi, ek, sel, ntiles);
-    }
-    MI_REQUIRE(whole, "native FFT: this kernel cannot run a subset of its tiles");
-    if (!fuse_forward && (splits() || padded) && (ek == EPI_NONE || ek == EPI_RATIO || ek == EPI_UPDATE) && epi_kind != EPI_TAPER_SHELL &&
-        out != nullptr && aligned && !no_xpipe) {
-        MI_TRY(pipe_tiles(padded, nullptr, &sel, &ntiles));
-        return x_pipelined(s, 2, t_spec, out, epi, ek, sel, ntiles);
+    XCall c;
+    c.fuse_forward = fuse_forward;
+    c.whole = !(part && part->mode != 0);
+    c.aligned = ((uintptr_t)epi.a % 16) == 0 && ((uintptr_t)out % 16) == 0;
+    c.ek = ek;
+    c.taper_shell = epi_kind == EPI_TAPER_SHELL;
+    c.has_out = out != nullptr;
+    const XRoute route = x_route(dims, sw, pw, c);
+    MI_REQUIRE(route != XRoute::no_subset, "native FFT: this kernel cannot run a subset of its tiles");
+    if (route == XRoute::pipe_fused || route == XRoute::pipe_inverse) {
+        TileSelect sel;
+        int ntiles = 0;
+        MI_TRY(pipe_tiles(pw.on != 0, route == XRoute::pipe_fused ? part : nullptr, &sel, &ntiles));
+        return x_pipelined(s, route == XRoute::pipe_fused ? 0 : 2, t_spec, out, epi, ek, sel, ntiles);
     }
     const unsigned xtiles = (unsigned)((size_t)dims.nz * (dims.ny / dims.ty));
     const size_t xl = lds_bytes(dims.ty, dims.hx);

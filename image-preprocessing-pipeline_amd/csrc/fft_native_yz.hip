@@ -289,11 +289,11 @@ __global__ __launch_bounds__(kThreadsY, 4) void k_y_pair(const float2* __restric
 }
 
 // one launch of the y kernel of the layout and direction: `ycols` work-groups on the planes and columns that `d` names
-int y_launch(const NativeFft& f, hipStream_t s, bool inverse, bool paired, unsigned ycols, const NativeDims& d, const float2* src, float2* dst) {
+int y_launch(const NativeFft& f, hipStream_t s, bool inverse, YRoute route, unsigned ycols, const NativeDims& d, const float2* src, float2* dst) {
     const size_t yl = lds_bytes(d.tc, d.ny);
     return y_case(d, [&](auto lg, auto r) {
         constexpr int LG = lg(), R = r();
-        if (paired)
+        if (route == YRoute::pair)
             return inverse ? launch_lds(k_y_pair<LG, R, true>, ycols, kThreadsY, yl, s, "k_y_pair<inv>", src, dst, d, f.tw_y)
                            : launch_lds(k_y_pair<LG, R, false>, ycols, kThreadsY, yl, s, "k_y_pair<fwd>", src, dst, d, f.tw_y);
         return inverse ? launch_lds(k_y_pass<LG, R, true>, ycols, kThreadsY, yl, s, "k_y_pass<inv>", src, dst, d, f.tw_y)
@@ -431,11 +431,6 @@ __global__ __launch_bounds__(kThreadsXZ, kWavesXZ) void k_z_conv(const float2* _
 // centre's offset from the grid origin: G holds the two real factors of a pair (float2 instead of float4: 4 instead of 8 B per
 // voxel of OTF traffic, a sixth of this pass) and the ramp exp(-2 pi i (kx dx/Fx + ky dy/Fy + kz dz/Fz)) is put back from three
 // small per-axis tables (x and y: scalar loads, z: one look-up per lane and tile).
-constexpr bool z_pipe_even(int L) {
-    // the real form needs line-uniform phases per item: either the lines divide the work-group evenly, or every wave owns one
-    // pair of lines (the WP layout of k_z_conv_pipe)
-    return (L % 64 == 0) && ((z_tile_lines(L) * L) % kThreadsXZ == 0) && ((kThreadsXZ % L == 0) || z_tile_lines(L) == kThreadsXZ / 64);
-}
 struct RealOtf {
     const float2* g;     // [xk][py][pz] {Ra, Rb}
     const float2* ph_x;  // by xk
@@ -942,14 +937,7 @@ RealOtf real_otf_args(const NativeFft& f, bool adj_slot) {
     return ro;
 }
 
-// The paired z pass: its lengths, each with the threads per work-group and whether the z ramp has its LDS table (PHL).
-// Lines of up to 576 points: 8 waves on a 64-KB tile, two work-groups per CU (576 points: the LDS phase table would cost the
-// second work-group); 768 and 1152 points: 16 waves, one line per wave; 1024 points: 8 waves again, a line pair per wave -- with
-// the 16-point top stage a lane's 16 float4 are exactly that stage's points of two lines, so it runs on the registers of the
-// global access like the 512-point pass (246 registers, one work-group per CU): 5.60 -> 5.11 ms on 1024 x 576 x 4096 against the
-// 16-wave form, A / B in one process.
-#define MI_ZQ_CASES(M) M(6, 1, 512, true) M(7, 1, 512, true) M(8, 1, 512, true) M(9, 1, 512, true) M(10, 1, 512, true) \
-    M(6, 3, 512, true) M(7, 3, 512, true) M(8, 3, 1024, true) M(6, 9, 512, false) M(7, 9, 1024, true)
+// the paired z pass: one case per length of MI_ZQ_CASES (fft_native_route.h), with its threads per work-group and its PHL flag
 #define MI_ZQ_CALL(LG, R, NTH, PH) case LG * 16 + R: return f(Int<LG>{}, Int<R>{}, Int<NTH>{}, std::bool_constant<PH>{});
 template <class F>
 int z_pair_case(const NativeDims& d, F&& f) {
@@ -959,15 +947,16 @@ int z_pair_case(const NativeDims& d, F&& f) {
 
 }  // namespace
 
-int NativeFft::y_pass(hipStream_t s, bool inverse, bool paired, const float2* src_o, float2* dst_o, int xk0, int xkn) {
+int NativeFft::y_pass(hipStream_t s, bool inverse, YRoute route, const float2* src_o, float2* dst_o, int xk0, int xkn) {
     const int Hx = dims.hx, L = dims.nz;
     if (xkn < 0) xkn = Hx / 2 + 1;
+    const bool paired = route == YRoute::pair;
     MI_REQUIRE(paired || (xk0 == 0 && xkn == Hx / 2 + 1), "native FFT: only the paired y pass runs on a chunk of planes");
     const unsigned ycols = paired ? (unsigned)((size_t)xkn * (L / (dims.tc / 2))) : (unsigned)((size_t)L * Hx / dims.tc);
     NativeDims d = dims;
     d.xk0 = xk0;
     d.xkn = xkn;
-    return y_launch(*this, s, inverse, paired, ycols, d, src_o ? src_o : S.as<float2>(), dst_o ? dst_o : t_spec);
+    return y_launch(*this, s, inverse, route, ycols, d, src_o ? src_o : S.as<float2>(), dst_o ? dst_o : t_spec);
 }
 
 // forward y pass of a range of z planes (the z-chunked halo exchange: a chunk's columns are transformed as soon as its halo rows
@@ -982,7 +971,7 @@ int NativeFft::y_forward_planes(hipStream_t s, int z0, int nzc) {
     NativeDims d = dims;
     d.yz0 = z0;
     d.z_in_hi = std::min(dims.z_in_hi, z0 + nzc);   // (work-groups of the last, partial granule stop here)
-    return y_launch(*this, s, false, paired, ycols, d, S.as<float2>(), t_spec);
+    return y_launch(*this, s, false, y_route(dims), ycols, d, S.as<float2>(), t_spec);
 }
 
 
@@ -1002,61 +991,58 @@ int NativeFft::z_conv(hipStream_t s, bool conj_otf, const float2* src_o, float2*
     const float2* twz = tw_z;
     const int cj = (conj_otf && !have_adj) ? 1 : 0;
     const RealOtf ro = real_otf ? real_otf_args(*this, adj_slot) : RealOtf{};
-    if (dims.paired) {
-        const int ntiles = xkn * (M / kPairLines);
-        const bool phl = !(dims.lz2 == 6 && dims.r3z == 9);  // (576-point lines: see MI_ZQ_CASES)
-        const size_t lds = lds_bytes(2 * kPairLines, L) + (real_otf && phl ? sizeof(float2) * (size_t)L : 0);
-        const int per_cu = std::max(1, std::min(2, (int)(kLdsOneWg / lds)));  // 8 waves of 128 registers each: two fit a CU
-        const unsigned grid = (unsigned)std::min(ntiles, per_cu * n_cu);
-        int* ctr_p = nullptr;
-        {
-            static const char* env_dyn = std::getenv("MI_Z_DYN");
-            if (env_dyn ? atoi(env_dyn) != 0 : z_dynamic) {
+    switch (z_route(dims, sw, real_otf)) {
+        case ZRoute::pair_pipe:
+        case ZRoute::pair_pipe_real: {
+            const int ntiles = xkn * (M / kPairLines);
+            bool phl = true;  // (576-point lines have no LDS phase table: MI_ZQ_CASES)
+            z_pair_takes(dims.lz2, dims.r3z, nullptr, &phl);
+            const size_t lds = lds_bytes(2 * kPairLines, L) + (real_otf && phl ? sizeof(float2) * (size_t)L : 0);
+            const int per_cu = std::max(1, std::min(2, (int)(kLdsOneWg / lds)));  // 8 waves of 128 registers each: two fit a CU
+            const unsigned grid = (unsigned)std::min(ntiles, per_cu * n_cu);
+            int* ctr_p = nullptr;
+            if (z_tiles_dynamic(sw)) {
                 if (!ctr.p) MI_TRY(ctr.alloc(256));
                 ctr_p = ctr.as<int>() + 16 + 4 * (ctr_slot & 7);
                 MI_HIP(hipMemsetAsync(ctr_p, 0, sizeof(int), s));
             }
+            return z_pair_case(dims, [&](auto lg, auto r, auto nth, auto ph_lds) {
+                constexpr int LG = lg(), R = r(), NTH = nth();
+                constexpr bool PH = ph_lds();
+                return real_otf ? launch_lds(k_z_pair_pipe<LG, R, true, NTH, kPairLines, PH>, grid, NTH, lds, s, "k_z_pair_pipe<real OTF>", Tp, Sp, Gp,
+                                             d, twz, cj, ntiles, ro, ctr_p)
+                                : launch_lds(k_z_pair_pipe<LG, R, false, NTH, kPairLines, PH>, grid, NTH, lds, s, "k_z_pair_pipe", Tp, Sp, Gp, d,
+                                             twz, cj, ntiles, ro, ctr_p);
+            });
         }
-        return z_pair_case(dims, [&](auto lg, auto r, auto nth, auto ph_lds) {
-            constexpr int LG = lg(), R = r(), NTH = nth();
-            constexpr bool PH = ph_lds();
-            return real_otf ? launch_lds(k_z_pair_pipe<LG, R, true, NTH, kPairLines, PH>, grid, NTH, lds, s, "k_z_pair_pipe<real OTF>", Tp, Sp, Gp,
-                                         d, twz, cj, ntiles, ro, ctr_p)
-                            : launch_lds(k_z_pair_pipe<LG, R, false, NTH, kPairLines, PH>, grid, NTH, lds, s, "k_z_pair_pipe", Tp, Sp, Gp, d,
-                                         twz, cj, ntiles, ro, ctr_p);
-        });
+        case ZRoute::conv_pipe:
+        case ZRoute::conv_pipe_real: {
+            const int ntiles = (int)ztiles;
+            const unsigned grid = (unsigned)std::min(ntiles, n_cu);
+            return z_case(dims, [&](auto lg, auto r) {
+                constexpr int LG = lg(), R = r();
+                if constexpr (z_pipe_even(R << LG)) {
+                    if (real_otf)
+                        return launch_lds(k_z_conv_pipe<LG, R, true>, grid, kThreadsXZ, zl, s, "k_z_conv_pipe<real OTF>", Tp, Sp, Gp, d, twz, cj, ntiles, ro);
+                }
+                return launch_lds(k_z_conv_pipe<LG, R, false>, grid, kThreadsXZ, zl, s, "k_z_conv_pipe", Tp, Sp, Gp, d, twz, cj, ntiles, ro);
+            });
+        }
+        case ZRoute::conv:
+            return z_case(dims, [&](auto lg, auto r) {
+                return launch_lds(k_z_conv<lg(), r(), false>, ztiles, kThreadsXZ, zl, s, "k_z_conv", Tp, Sp, Gp, d, twz, cj, (float4*)nullptr, 0.0f);
+            });
+        case ZRoute::real_needs_pipe: break;
     }
-    if (z_pipelined()) {
-        const int ntiles = (int)ztiles;
-        const unsigned grid = (unsigned)std::min(ntiles, n_cu);
-        return z_case(dims, [&](auto lg, auto r) {
-            constexpr int LG = lg(), R = r();
-            if constexpr (z_pipe_even(R << LG)) {
-                if (real_otf)
-                    return launch_lds(k_z_conv_pipe<LG, R, true>, grid, kThreadsXZ, zl, s, "k_z_conv_pipe<real OTF>", Tp, Sp, Gp, d, twz, cj, ntiles, ro);
-            }
-            return launch_lds(k_z_conv_pipe<LG, R, false>, grid, kThreadsXZ, zl, s, "k_z_conv_pipe", Tp, Sp, Gp, d, twz, cj, ntiles, ro);
-        });
-    }
-    MI_REQUIRE(!real_otf, "native FFT: the real OTF form needs the pipelined z pass");
-    return z_case(dims, [&](auto lg, auto r) {
-        return launch_lds(k_z_conv<lg(), r(), false>, ztiles, kThreadsXZ, zl, s, "k_z_conv", Tp, Sp, Gp, d, twz, cj, (float4*)nullptr, 0.0f);
-    });
-}
-
-bool NativeFft::z_pipelined() const {
-    static const bool no_pipe = std::getenv("MI_FFT_NO_PIPE") != nullptr;
-    return dims.paired || (dims.dbg == 0 && !no_pipe && dims.tl == z_tile_lines(dims.nz));
+    return fail(MI_ERR_INVALID, "native FFT: the real OTF form needs the pipelined z pass");
 }
 
 // Tries the real form of the OTF(s): `delta` = offset (x, y, z) of the PSF's centre sample from the grid origin.  Keeps the
 // complex form when the PSF is not mirror-symmetric about that sample (the imaginary parts left after removing the phase ramp
 // exceed the rounding noise of the transform) or when the z pass of this shape cannot take it.
 int NativeFft::try_real_otf(hipStream_t s, const int delta[3]) {
-    const bool off = std::getenv("MI_FFT_COMPLEX_OTF") != nullptr;
     const int Hx = dims.hx, M = dims.ny, L = dims.nz;
-    const bool even = dims.paired != 0 || z_pipe_even(L);
-    if (off || !z_pipelined() || !even) return MI_OK;
+    if (!real_otf_possible(dims, sw)) return MI_OK;
     // phase tables exp(-2 pi i (k delta mod F) / F) in double on the host: x by xk <= Hx/2 (F = 2 Hx), y by ky, z by kz
     const int nx = Hx / 2 + 1;
     std::vector<float2> h((size_t)nx + M + L);
@@ -1113,7 +1099,7 @@ int NativeFft::build_otf(hipStream_t s, const float* placed, bool adjoint_slot, 
 int NativeFft::spectrum(hipStream_t s, const float* vol, float4* Gp, float scale) {
     MI_REQUIRE(!pw.on, "native FFT: spectra are taken on the unpadded grid (before the pad window is set)");
     MI_TRY(x_forward(s, vol));
-    MI_TRY(y_pass(s, false, false));  // (k_z_conv<build> reads the plain [px][z][py] layout)
+    MI_TRY(y_pass(s, false, YRoute::pass));  // (k_z_conv<build> reads the plain [px][z][py] layout)
     const unsigned ztiles = (unsigned)((size_t)(dims.hx / 2 + 1) * (dims.ny / dims.tl));
     return z_case(dims, [&](auto lg, auto r) {
         return launch_lds(k_z_conv<lg(), r(), true>, ztiles, kThreadsXZ, lds_bytes(2 * dims.tl, dims.nz), s, "k_z_conv<build>", (const float2*)t_spec,

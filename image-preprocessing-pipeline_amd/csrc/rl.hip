@@ -352,6 +352,30 @@ extern "C" int mi_rl_otf_is_real(mi_rl_ctx* ctx) {
     return ctx && ctx->engine == MI_ENGINE_FFT && ctx->fft->native && ctx->fft->native->real_otf ? 1 : 0;
 }
 
+extern "C" int mi_rl_fft_route(mi_rl_ctx* ctx, mi_fft_route* out) {
+    MI_REQUIRE(ctx && out, "mi_rl_fft_route: null pointer");
+    *out = mi_fft_route{};
+    if (!(ctx->engine == MI_ENGINE_FFT && ctx->fft && ctx->fft->native)) return MI_OK;
+    const NativeFft& f = *ctx->fft->native;
+    const ZRoute z = z_route(f.dims, f.sw, f.real_otf);
+    XCall fused;
+    fused.fuse_forward = true;
+    fused.ek = EPI_RATIO;
+    out->native = 1;
+    out->paired = f.dims.paired;
+    out->z_kernel = z == ZRoute::conv ? 0 : (z == ZRoute::conv_pipe || z == ZRoute::conv_pipe_real) ? 1 : 2;
+    out->real_otf = f.real_otf ? 1 : 0;
+    out->x_pipelined = x_route(f.dims, f.sw, f.pw, fused) == XRoute::pipe_fused ? 1 : 0;
+    out->x_splits = f.splits() ? 1 : 0;
+    out->x_dynamic = x_tiles_dynamic(f.sw) ? 1 : 0;
+    out->z_dynamic = z_tiles_dynamic(f.sw) ? 1 : 0;
+    out->pruned = f.pw.on && !f.sw.no_prune ? 1 : 0;
+    out->ty = f.dims.ty;
+    out->tc = f.dims.tc;
+    out->tl = f.dims.tl;
+    return MI_OK;
+}
+
 extern "C" int mi_rl_sharded_begin(mi_rl_ctx* ctx, void* stream, const float* bl) {
     NativeFft* nf = nullptr;
     MI_TRY(sharded_native(ctx, &nf));
@@ -497,7 +521,7 @@ extern "C" int mi_rl_sharded_stage(mi_rl_ctx* ctx, void* stream, float* bl, int 
     }
     if (stage == 1) {
         MI_TRY(nf->z_conv(s, update != 0));
-        return nf->y_pass(s, true, nf->dims.paired != 0);
+        return nf->y_pass(s, true, y_route(nf->dims));
     }
     MI_REQUIRE(bl, "mi_rl_sharded_stage: null pointer");
     MI_REQUIRE(edges && edges[0] >= 0 && edges[0] < edges[1] && edges[1] <= edges[2] && edges[2] < edges[3] && edges[3] <= ctx->n[1],

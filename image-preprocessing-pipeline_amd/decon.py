@@ -370,6 +370,14 @@ class RLContext:
         return bool(lib().mi_rl_otf_is_real(self._h))
 
     @property
+    def fft_route(self) -> dict:
+        """What the context's FFT plan does (``mi_rl_fft_route``): kernel family of the z pass, layouts, tile hand-out, tile sizes --
+        decided from the environment at the moment the context was created."""
+        r = capi.FftRoute()
+        check(lib().mi_rl_fft_route(self._h, C.byref(r)))
+        return {name: int(getattr(r, name)) for name, _ in capi.FftRoute._fields_}
+
+    @property
     def spectrum_row_floats(self) -> int:
         """float32 words of one row (all z, all x frequencies) of the x-transformed input buffer."""
         return int(lib().mi_rl_spectrum_row_floats(self._h))

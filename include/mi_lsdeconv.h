@@ -167,6 +167,17 @@ int mi_rl_fuses(mi_rl_ctx* ctx);
 /* 1 when the context keeps its OTF in the real form (PSF mirror-symmetric about its centre sample: 2 floats per spectrum pair
  * plus per-axis phase tables instead of 4 floats; the z pass then moves 10 instead of 12 bytes per voxel). */
 int mi_rl_otf_is_real(mi_rl_ctx* ctx);
+/* What the context's FFT plan does, from the plan's own record (the switches are those of the environment at the moment the
+ * context was created and hold for its whole life): native 1 = the hand-written pipeline (everything else is 0 when it is not);
+ * paired = mi_rl_pair_layout; z_kernel 0 k_z_conv, 1 k_z_conv_pipe, 2 k_z_pair_pipe; real_otf = mi_rl_otf_is_real; x_pipelined 1 = a
+ * whole, aligned fused x pass runs as the persistent kernel; x_splits 1 = ... and can run a subset of its tiles (mi_rl_fuses == 2);
+ * x_dynamic / z_dynamic 1 = the persistent x launches / the paired z pass take their tiles from a device counter (MI_X_DYN /
+ * MI_Z_DYN = 0: at a fixed stride); pruned 1 = the passes skip what a padded grid leaves empty; ty, tc, tl: rows, columns and lines
+ * of the x, y and z tiles. */
+typedef struct {
+    int native, paired, z_kernel, real_otf, x_pipelined, x_splits, x_dynamic, z_dynamic, pruned, ty, tc, tl;
+} mi_fft_route;
+int mi_rl_fft_route(mi_rl_ctx* ctx, mi_fft_route* out);
 int mi_rl_sharded_begin(mi_rl_ctx* ctx, void* stream, const float* bl);
 int mi_rl_sharded_ratio(mi_rl_ctx* ctx, void* stream, const float* bl, int part, const int* edge_rows);
 int mi_rl_sharded_update(mi_rl_ctx* ctx, void* stream, float* bl, int more, int part, const int* edge_rows);

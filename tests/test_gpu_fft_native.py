@@ -312,18 +312,21 @@ def test_tile_hand_out_is_bit_identical(dev, shape, monkeypatch):
     psf = R.gaussian_psf((5, 7, 5), (1.0, 1.5, 1.0))
     vol = torch.from_numpy(R.bead_volume(shape, seed=23, psf=psf)).to(dev)
 
-    def run():
+    def run(dynamic):
         ctx = decon.RLContext(shape, psf, None, boundary=capi.BOUNDARY_CIRCULAR, engine=capi.ENGINE_FFT, device=dev)
         assert ctx.fuses and ctx.pair_layout
+        route = ctx.fft_route   # (a plan keeps the switches of the moment it was created)
+        assert route["x_pipelined"] == 1 and route["z_kernel"] == 2
+        assert (route["x_dynamic"], route["z_dynamic"]) == (dynamic, dynamic), route
         bl = vol.clone()
         ctx.iterate(bl, None, 3)
         return bl
 
-    ref = run()
+    ref = run(1)
     for env in ({"MI_X_DYN": "0", "MI_Z_DYN": "0"},):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
-        got = run()
+        got = run(0)
         for k in env:
             monkeypatch.delenv(k)
         assert torch.equal(got, ref), env

@@ -58,3 +58,61 @@ def test_convolutions_and_iterations_match_float64_on_either_side_of_the_thresho
     ctx.iterate(bl, None, 5)
     assert_close(bl.cpu().numpy(), want, what="5 iterations")
     ctx.close()
+
+
+# what mi_rl_fft_route must report for a circular context with the symmetric 5 x 7 x 5 Gaussian PSF: (64, 64, 128) is in the paired
+# range of z, (32, 64, 128) below it (and its 32-point lines cannot take the real OTF in k_z_conv_pipe); tiles 16 / 16 / 16 on both
+ROUTE_SHAPES = [(64, 64, 128), (32, 64, 128)]
+ROUTE_SWITCHES = [None, "MI_FFT_NO_PAIR", "MI_FFT_NO_PIPE", "MI_FFT_NO_XPIPE", "MI_FFT_COMPLEX_OTF"]
+
+
+def _expected_route(shape, switch):
+    in_pair_range = shape[0] == 64
+    paired = int(in_pair_range and switch not in ("MI_FFT_NO_PAIR", "MI_FFT_NO_PIPE"))
+    piped = int(switch != "MI_FFT_NO_PIPE")
+    return dict(native=1, paired=paired, z_kernel=2 if paired else piped, real_otf=int(in_pair_range and piped and switch != "MI_FFT_COMPLEX_OTF"),
+                x_pipelined=int(piped and switch != "MI_FFT_NO_XPIPE"), x_splits=piped, x_dynamic=1, z_dynamic=1, pruned=0, ty=16, tc=16, tl=16)
+
+
+@pytest.fixture(scope="module")
+def default_route_results():
+    """Per shape: (volume, three fused iterations of a context created without any switch), computed once."""
+    from ipp_amd import capi, decon
+    dev = torch.device("cuda", 0)
+    psf = R.gaussian_psf((5, 7, 5), (1.0, 1.5, 1.0))
+    out = {}
+    for shape in ROUTE_SHAPES:
+        vol = torch.from_numpy(R.bead_volume(shape, seed=23, psf=psf)).to(dev)
+        ctx = decon.RLContext(shape, psf, None, boundary=capi.BOUNDARY_CIRCULAR, engine=capi.ENGINE_FFT, device=dev)
+        bl = vol.clone()
+        ctx.iterate(bl, None, 3)
+        ctx.close()
+        out[shape] = (vol, bl)
+    return out
+
+
+@pytest.mark.parametrize("switch", ROUTE_SWITCHES, ids=[s or "default" for s in ROUTE_SWITCHES])
+@pytest.mark.parametrize("shape", ROUTE_SHAPES)
+def test_fft_route_reports_what_each_switch_does(dev, shape, switch, default_route_results, monkeypatch):
+    """mi_rl_fft_route under each route switch, and three fused iterations against the default route's: within the bounds between
+    layouts of tests/test_gpu_pair_layout.py, bit for bit for MI_FFT_NO_XPIPE (same arithmetic, every stage in LDS:
+    tests/test_gpu_x_register_stage.py).  The switch is set only while the context is created: the plan keeps it."""
+    from ipp_amd import capi, decon
+    psf = R.gaussian_psf((5, 7, 5), (1.0, 1.5, 1.0))
+    if switch:
+        monkeypatch.setenv(switch, "1")
+    ctx = decon.RLContext(shape, psf, None, boundary=capi.BOUNDARY_CIRCULAR, engine=capi.ENGINE_FFT, device=dev)
+    if switch:
+        monkeypatch.delenv(switch)
+    route = ctx.fft_route
+    print(shape, switch, route)
+    assert route == _expected_route(shape, switch)
+    assert (ctx.pair_layout, ctx.otf_is_real, ctx.fuses) == (bool(route["paired"]), bool(route["real_otf"]), 2 if route["x_splits"] else 1)
+    vol, want = default_route_results[shape]
+    bl = vol.clone()
+    ctx.iterate(bl, None, 3)
+    ctx.close()
+    if switch in (None, "MI_FFT_NO_XPIPE"):
+        assert torch.equal(bl, want)
+    else:
+        assert_close(bl.cpu().numpy(), want.cpu().numpy().astype(np.float64), rel=2e-5, rel_l2=5e-6, pt_rel=5e-5)
