@@ -62,10 +62,13 @@ class PystripeParams(C.Structure):
                 ("bidirectional", C.c_int), ("down_y", C.c_int), ("down_x", C.c_int), ("down_method", C.c_int),
                 ("use_flat", C.c_int), ("dark", C.c_float), ("convert_to_16bit", C.c_int), ("convert_to_8bit", C.c_int),
                 ("bit_shift", C.c_int), ("out_dtype", C.c_int), ("flip_upside_down", C.c_int), ("rotate", C.c_int),
-                ("log_output", C.c_int), ("max_batch", C.c_int), ("keep_uniform", C.c_int)]
+                ("log_output", C.c_int), ("max_batch", C.c_int), ("keep_uniform", C.c_int), ("bleach_frequency", C.c_double),
+                ("bleach_clip_min", C.c_double), ("bleach_clip_med", C.c_double), ("bleach_clip_max", C.c_double),
+                ("bleach_max_method", C.c_int)]
 
 
 PS_MAX_LEVELS = 24  # MI_PS_MAX_LEVELS
+PS_BLEACH_LDS_ROW = 20436  # MI_PS_BLEACH_LDS_ROW
 
 
 class PystripeInfo(C.Structure):
@@ -73,7 +76,7 @@ class PystripeInfo(C.Structure):
     _fields_ = [("ny", C.c_int), ("nx", C.c_int), ("base_pad", C.c_int), ("pad_y", C.c_int), ("pad_x", C.c_int),
                 ("padded_ny", C.c_int), ("padded_nx", C.c_int), ("levels", C.c_int), ("coef_ny", C.c_int * PS_MAX_LEVELS),
                 ("coef_nx", C.c_int * PS_MAX_LEVELS), ("out_ny", C.c_int), ("out_nx", C.c_int), ("out_dtype", C.c_int),
-                ("integer_kind", C.c_int), ("max_batch", C.c_int), ("scratch_bytes_per_tile", C.c_size_t)]
+                ("integer_kind", C.c_int), ("max_batch", C.c_int), ("scratch_bytes_per_tile", C.c_size_t), ("bleach_long_rows", C.c_int)]
 
 
 class LightsheetParams(C.Structure):

@@ -17,6 +17,10 @@
 //             its nine k.  waverec2's trim of the approximation is a smaller extent read with the wider stride.
 //   store     the last synthesis level computes only the un-padded window and finishes every sample in registers: expm1, rint + clip
 //             (integer tiles), dark, 8 / 16-bit conversion, flip and rotation in the store address.
+//   bleach    correct_bleaching (:501): with it on, the last synthesis level stores the log image L instead (at sigma == (0, 0)
+//             L is log1p on load and never stored); a work-group per row runs sosfiltfilt's forward-backward first-order
+//             recurrence in float64 as a scan of affine maps over the clipped, odd-extended row in LDS and writes F and its row
+//             maximum; a block per tile reduces the maxima; the apply pass hands (L / F) * max F to the same store.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -61,6 +65,7 @@ Filters make_filters() {
 }
 
 enum { MAP_IDENTITY = 4 };
+enum { SRC_KEY = 3 };   // Src::dtype beside mi_pystripe_dtype: order-preserving keys of floats (float_key)
 enum { OUT_FLOAT = 0, OUT_TO8 = 1, OUT_CLIPCAST = 2 };
 
 __device__ __forceinline__ int sym_index(int j, int n) {   // half-point symmetric extension, any distance
@@ -95,11 +100,19 @@ struct Src {
     int pad, mode, logp;
 };
 
+// float -> unsigned whose order is the floats' order for either sign (0 lies below every float's key)
+__device__ __forceinline__ unsigned float_key(float f) {
+    const unsigned b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key_float(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
 __device__ __forceinline__ float src_load(const Src& s, i64 tile, int y, int x) {
     const i64 o = tile * s.tile_stride + (i64)y * s.row_stride + x;
     float v;
     if (s.dtype == MI_PS_U16) v = (float)static_cast<const uint16_t*>(s.p)[o];
     else if (s.dtype == MI_PS_U8) v = (float)static_cast<const uint8_t*>(s.p)[o];
+    else if (s.dtype == SRC_KEY) v = key_float(static_cast<const unsigned*>(s.p)[o]);
     else v = static_cast<const float*>(s.p)[o];
     return s.logp ? log1pf(v) : v;
 }
@@ -421,6 +434,208 @@ __global__ void __launch_bounds__(256) syn_rows_kernel(const float* lo1, const f
     }
 }
 
+// ---- bleach correction (correct_bleaching :501, butter_lowpass_filter :492) -----------------------------------------------------
+
+constexpr int kBleachExt = 6;                          // sosfiltfilt's padlen for one section
+constexpr int kBleachMaxThreads = 1024;
+constexpr size_t kBleachLds = 160 * 1024;              // all of a CU's LDS
+constexpr size_t kBleachTotals = (kBleachMaxThreads / 64) * sizeof(double2);   // the scan's wave totals, behind the row
+constexpr int kBleachSeg = (int)((kBleachLds - kBleachTotals) / sizeof(double));   // doubles of a row (or of a segment of it) in LDS
+static_assert(kBleachSeg - 2 * kBleachExt == MI_PS_BLEACH_LDS_ROW, "MI_PS_BLEACH_LDS_ROW is derived from the LDS request");
+
+struct Bleach {
+    double b, a;              // y = b u + z;  z' = b u + a y
+    float lo, med, hi;        // G = clip(L == 0 ? med : L, lo, hi)
+};
+
+__device__ __forceinline__ double bleach_sample(const Src& s, const Bleach& q, i64 tile, int line, int j) {
+    float v = src_load(s, tile, line, j);
+    if (v == 0.f) v = q.med;
+    return (double)fminf(fmaxf(v, q.lo), q.hi);
+}
+
+// sample p of the line extended by 6 per side (scipy's odd_ext): 2 x[0] - x[6 .. 1], x, 2 x[n-1] - x[n-2 .. n-7]
+__device__ __forceinline__ double bleach_extended(const Src& s, const Bleach& q, i64 tile, int line, int n, int p) {
+    const int j = p - kBleachExt;
+    if (j < 0) return 2.0 * bleach_sample(s, q, tile, line, 0) - bleach_sample(s, q, tile, line, -j);
+    if (j >= n) return 2.0 * bleach_sample(s, q, tile, line, n - 1) - bleach_sample(s, q, tile, line, 2 * (n - 1) - j);
+    return bleach_sample(s, q, tile, line, j);
+}
+
+// One direction of the recurrence over u[0 .. m) in LDS, in place, from the state z0; returns the state behind the last sample.
+// REV walks from u[m - 1] down.  A chunk of `chunk` samples (odd: the threads' 8-byte accesses then fall on different banks)
+// per thread: run from state 0 for the chunk's affine map z -> A z + P, scan the maps over the group (shuffles inside a wave, the
+// wave totals through `tot`), run again from the carried state.  Every thread of the group calls it.
+template <bool REV>
+__device__ double bleach_pass(double* u, int m, int chunk, double z0, const Bleach& q, double2* tot) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+    const int i0 = min(m, tid * chunk), i1 = min(m, i0 + chunk);
+    double A = 1.0, P = 0.0;
+    for (int i = i0; i < i1; ++i) {
+        const double x = u[REV ? m - 1 - i : i];
+        const double y = q.b * x + P;
+        P = q.b * x + q.a * y;
+        A *= q.a;
+    }
+    // inclusive scan inside the wave: (Ao, Po) of the lanes before, then (A, P)
+    for (int d = 1; d < 64; d <<= 1) {
+        const double Ao = __shfl_up(A, d), Po = __shfl_up(P, d);
+        if (lane >= d) {
+            P = A * Po + P;
+            A = A * Ao;
+        }
+    }
+    if (lane == 63) tot[wave] = make_double2(A, P);
+    double Ae = __shfl_up(A, 1), Pe = __shfl_up(P, 1);   // the lanes before this one
+    if (lane == 0) { Ae = 1.0; Pe = 0.0; }
+    __syncthreads();
+    double z = z0, zend = z0;
+    for (int w = 0; w < nwaves; ++w) {
+        const double2 t = tot[w];
+        zend = t.x * zend + t.y;
+        if (w + 1 == wave) z = zend;
+    }
+    z = Ae * z + Pe;
+    for (int i = i0; i < i1; ++i) {
+        const int at = REV ? m - 1 - i : i;
+        const double x = u[at];
+        const double y = q.b * x + z;
+        z = q.b * x + q.a * y;
+        u[at] = y;
+    }
+    __syncthreads();
+    return zend;
+}
+
+// sosfiltfilt of line blockIdx.x of tile blockIdx.y: n samples through `s`, F as float32 (row stride f_row) and the line's maximum
+// of F (lmax may be null).  len = n + 12 <= seg: the whole extended line stays in LDS.  Otherwise segments of seg samples go through
+// LDS left to right with the carried state, the forward result goes to fwd (len doubles per line), and the backward pass takes it
+// from there in segments right to left.
+__global__ void __launch_bounds__(kBleachMaxThreads) bleach_filter_kernel(Src s, int n, int seg, int chunk, Bleach q, float* F, i64 f_tile_stride,
+                                                                          int f_row, float* lmax, i64 lmax_tile_stride, double* fwd,
+                                                                          i64 fwd_tile_stride) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double* u = reinterpret_cast<double*>(smem);
+    const int len = n + 2 * kBleachExt, cap = min(len, seg);
+    double2* tot = reinterpret_cast<double2*>(u + cap + (cap & 1));
+    const int line = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+    const i64 tile = blockIdx.y;
+    float* f = F + tile * f_tile_stride + (i64)line * f_row;
+    float mx = -INFINITY;
+    if (len <= seg) {
+        for (int p = tid; p < len; p += T) u[p] = bleach_extended(s, q, tile, line, n, p);
+        __syncthreads();
+        bleach_pass<false>(u, len, chunk, (1.0 - q.b) * u[0], q, tot);
+        bleach_pass<true>(u, len, chunk, (1.0 - q.b) * u[len - 1], q, tot);
+        for (int j = tid; j < n; j += T) {
+            const float v = (float)u[j + kBleachExt];
+            f[j] = v;
+            mx = fmaxf(mx, v);
+        }
+    } else {
+        double* y = fwd + tile * fwd_tile_stride + (i64)line * len;
+        double z = (1.0 - q.b) * bleach_extended(s, q, tile, line, n, 0);
+        for (int s0 = 0; s0 < len; s0 += seg) {
+            const int m = min(seg, len - s0);
+            for (int p = tid; p < m; p += T) u[p] = bleach_extended(s, q, tile, line, n, s0 + p);
+            __syncthreads();
+            z = bleach_pass<false>(u, m, chunk, z, q, tot);
+            for (int p = tid; p < m; p += T) y[s0 + p] = u[p];
+            __syncthreads();
+        }
+        // the forward result written above is read back by other threads of this group
+        __threadfence_block();
+        __syncthreads();
+        z = (1.0 - q.b) * y[len - 1];
+        for (int s1 = len; s1 > 0; s1 -= seg) {
+            const int s0 = max(0, s1 - seg), m = s1 - s0;
+            for (int p = tid; p < m; p += T) u[p] = y[s0 + p];
+            __syncthreads();
+            z = bleach_pass<true>(u, m, chunk, z, q, tot);
+            for (int p = tid; p < m; p += T) {
+                const int j = s0 + p - kBleachExt;
+                if (j >= 0 && j < n) {
+                    const float v = (float)u[p];
+                    f[j] = v;
+                    mx = fmaxf(mx, v);
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (!lmax) return;
+    for (int d = 32; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
+    float* red = reinterpret_cast<float*>(tot);   // the last pass has left it
+    if ((tid & 63) == 0) red[tid >> 6] = mx;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < (T >> 6); ++w) mx = fmaxf(mx, red[w]);
+        lmax[tile * lmax_tile_stride + line] = mx;
+    }
+}
+
+// max method: the row and column maxima of L in one pass, as keys (zeroed before the launch).  A block covers 64 columns x 64 rows,
+// one wave per row at a time.
+__global__ void __launch_bounds__(256) bleach_maxima_kernel(Src s, int ny, int nx, unsigned* row_key, unsigned* col_key, i64 key_tile_stride) {
+    __shared__ float colmax[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = blockIdx.x * 64 + lane, y0 = blockIdx.y * 64;
+    const i64 tile = blockIdx.z;
+    float cm = -INFINITY;
+    for (int y = y0 + wave; y < min(ny, y0 + 64); y += 4) {
+        const float v = x < nx ? src_load(s, tile, y, x) : -INFINITY;
+        cm = fmaxf(cm, v);
+        float rm = v;
+        for (int d = 32; d >= 1; d >>= 1) rm = fmaxf(rm, __shfl_xor(rm, d));
+        if (lane == 0) atomicMax(&row_key[tile * key_tile_stride + y], float_key(rm));
+    }
+    colmax[wave][lane] = cm;
+    __syncthreads();
+    if (wave == 0 && x < nx) {
+        cm = fmaxf(fmaxf(colmax[0][lane], colmax[1][lane]), fmaxf(colmax[2][lane], colmax[3][lane]));
+        atomicMax(&col_key[tile * key_tile_stride + x], float_key(cm));
+    }
+}
+
+// M[tile] = max F.  max_method: F = ry (x) cx is never stored; a product of two factors is largest at a corner of their ranges and
+// float32 rounding keeps the order, so M is the largest of the four float32 products of the vectors' extremes -- for any signs.
+__global__ void __launch_bounds__(256) bleach_tilemax_kernel(const float* a, int na, const float* c, int nc, i64 tile_stride, int max_method,
+                                                             float* M) {
+    __shared__ float red[4][4];
+    const i64 tile = blockIdx.x;
+    const float* pa = a + tile * tile_stride;
+    float v[4] = {-INFINITY, INFINITY, -INFINITY, INFINITY};   // max a, min a, max c, min c
+    for (int i = threadIdx.x; i < na; i += 256) { v[0] = fmaxf(v[0], pa[i]); v[1] = fminf(v[1], pa[i]); }
+    if (max_method) {
+        const float* pc = c + tile * tile_stride;
+        for (int i = threadIdx.x; i < nc; i += 256) { v[2] = fmaxf(v[2], pc[i]); v[3] = fminf(v[3], pc[i]); }
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        v[0] = fmaxf(v[0], __shfl_xor(v[0], d)); v[1] = fminf(v[1], __shfl_xor(v[1], d));
+        v[2] = fmaxf(v[2], __shfl_xor(v[2], d)); v[3] = fminf(v[3], __shfl_xor(v[3], d));
+    }
+    if ((threadIdx.x & 63) == 0)
+        for (int e = 0; e < 4; ++e) red[threadIdx.x >> 6][e] = v[e];
+    __syncthreads();
+    if (threadIdx.x) return;
+    for (int w = 1; w < 4; ++w) {
+        v[0] = fmaxf(v[0], red[w][0]); v[1] = fminf(v[1], red[w][1]);
+        v[2] = fmaxf(v[2], red[w][2]); v[3] = fminf(v[3], red[w][3]);
+    }
+    M[tile] = max_method ? fmaxf(fmaxf(v[0] * v[2], v[0] * v[3]), fmaxf(v[1] * v[2], v[1] * v[3])) : v[0];
+}
+
+// (L / F) * M in float32, in that order, then the tail every filtered sample takes
+__global__ void __launch_bounds__(256) bleach_apply_kernel(Src s, const float* F, i64 f_tile_stride, const float* ry, const float* cx,
+                                                           i64 vec_tile_stride, const float* M, Sink k) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const i64 tile = blockIdx.z;
+    if (x >= k.nx || y >= k.ny) return;
+    const float f = ry ? ry[tile * vec_tile_stride + y] * cx[tile * vec_tile_stride + x] : F[tile * f_tile_stride + (i64)y * k.nx + x];
+    const float v = src_load(s, tile, y, x) / f;
+    sink_store(k, tile, y, x, v * M[tile]);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 
 int notch_rise_point(double sigma, double rise) {   // :670
@@ -449,14 +664,19 @@ struct Plan {
     int dev = 0, in_ny = 0, in_nx = 0, in_dtype = 0;
     mi_pystripe_params prm{};
     mi_pystripe_info info{};
-    bool filter = false, pre = false;
+    bool filter = false, pre = false, bleach = false;
     int passes = 0;
+    Bleach bq{};
     Filters f{};
     int h[MI_PS_MAX_LEVELS + 1] = {0}, w[MI_PS_MAX_LEVELS + 1] = {0};   // extents per level, [0] = padded image
     // per-tile scratch, offsets in floats
     size_t off_stage = 0, off_P = 0, off_rowL = 0, off_rowH = 0, off_A[MI_PS_MAX_LEVELS + 1] = {0}, off_cH[MI_PS_MAX_LEVELS + 1] = {0},
            off_cV[MI_PS_MAX_LEVELS + 1] = {0}, off_cD[MI_PS_MAX_LEVELS + 1] = {0};
     size_t sz_stage = 0, sz_P = 0, sz_row = 0, sz_A[MI_PS_MAX_LEVELS + 1] = {0}, sz_d[MI_PS_MAX_LEVELS + 1] = {0};
+    // bleach correction: the log image (with a stripe filter), F and its row maxima, or (max method) the maxima keys and the filtered
+    // vectors, rows first; the tile maximum; the forward result of lines too long for LDS (doubles, two floats each)
+    size_t off_L = 0, off_F = 0, off_lmax = 0, off_key = 0, off_vec = 0, off_M = 0, off_fwd = 0;
+    size_t sz_L = 0, sz_F = 0, sz_lmax = 0, sz_vec = 0, sz_fwd = 0;
     std::vector<NotchTab> tabs;   // [pass][level 1..L][axis 0: cH along -1, 1: cV along -2]
     DevBuf tw_buf, w_buf, scratch, varies;
     i64 cap = 0;
@@ -489,8 +709,27 @@ int derive(int ny_in, int nx_in, int in_dtype, const mi_pystripe_params& q, Plan
     I.max_batch = q.max_batch > 0 ? q.max_batch : 16;
     // grid limits: rows go to gridDim.y, tiles (twice, in the column synthesis) to gridDim.z
     MI_REQUIRE(I.max_batch <= 16384, "mi_pystripe: max_batch %d (at most 16384 tiles per launch)", I.max_batch);
+    P.bleach = q.bleach_frequency != 0;
+    if (P.bleach) {
+        MI_REQUIRE(q.bleach_frequency > 0 && q.bleach_frequency < 1, "mi_pystripe: bleach_frequency %g is not in (0, 1)", q.bleach_frequency);
+        MI_REQUIRE(q.bleach_clip_min >= 0, "mi_pystripe: bleach_clip_min %g is negative", q.bleach_clip_min);
+        MI_REQUIRE(q.bleach_clip_med > q.bleach_clip_min, "mi_pystripe: bleach_clip_med %g is not above bleach_clip_min %g", q.bleach_clip_med,
+                   q.bleach_clip_min);
+        MI_REQUIRE(q.bleach_clip_max > q.bleach_clip_med, "mi_pystripe: bleach_clip_max %g is not above bleach_clip_med %g", q.bleach_clip_max,
+                   q.bleach_clip_med);
+        // sosfiltfilt's padlen: a filtered line has more than 6 samples
+        MI_REQUIRE(I.nx > kBleachExt, "mi_pystripe: bleach correction filters rows of nx = %d samples (after down_sample); at least 7", I.nx);
+        MI_REQUIRE(!q.bleach_max_method || I.ny > kBleachExt,
+                   "mi_pystripe: bleach_max_method filters the column of ny = %d row maxima (after down_sample); at least 7", I.ny);
+        const double k = std::tan(M_PI * q.bleach_frequency / 2.0);
+        P.bq.b = k / (1.0 + k);
+        P.bq.a = (1.0 - k) / (1.0 + k);
+        P.bq.lo = (float)std::max(q.bleach_clip_min, std::log1p(1.0));
+        P.bq.med = (float)q.bleach_clip_med;
+        P.bq.hi = (float)q.bleach_clip_max;
+    }
     if (q.log_output) {
-        MI_REQUIRE(P.filter, "mi_pystripe: log_output needs a stripe filter (sigma > 0)");
+        MI_REQUIRE(P.filter || P.bleach, "mi_pystripe: log_output needs a stripe filter (sigma > 0) or the bleach correction");
         I.out_ny = I.ny; I.out_nx = I.nx; I.out_dtype = MI_PS_F32;
     } else {
         const bool swap = q.rotate == 90 || q.rotate == 270;
@@ -533,6 +772,24 @@ int derive(int ny_in, int nx_in, int in_dtype, const mi_pystripe_params& q, Plan
             P.off_cV[l] = take(P.sz_d[l]);
             P.off_cD[l] = take(P.sz_d[l]);
         }
+    }
+    if (P.bleach) {
+        const size_t npix = (size_t)I.ny * I.nx;
+        const int longest = q.bleach_max_method ? std::max(I.ny, I.nx) : I.nx;
+        I.bleach_long_rows = longest > MI_PS_BLEACH_LDS_ROW;
+        if (P.filter) { P.sz_L = npix; P.off_L = take(P.sz_L); }
+        if (q.bleach_max_method) {
+            P.sz_vec = (size_t)I.ny + I.nx;
+            P.off_key = take(P.sz_vec);
+            P.off_vec = take(P.sz_vec);
+            if (I.bleach_long_rows) P.sz_fwd = 2 * ((size_t)longest + 2 * kBleachExt);
+        } else {
+            P.sz_F = npix; P.off_F = take(P.sz_F);
+            P.sz_lmax = (size_t)I.ny; P.off_lmax = take(P.sz_lmax);
+            if (I.bleach_long_rows) P.sz_fwd = 2 * (size_t)I.ny * ((size_t)I.nx + 2 * kBleachExt);
+        }
+        P.off_M = take(1);
+        if (P.sz_fwd) P.off_fwd = take(P.sz_fwd);
     }
     I.scratch_bytes_per_tile = off * sizeof(float);
     // the output conversion (:1361-1369)
@@ -615,6 +872,53 @@ int run_notch(const Plan& P, hipStream_t st, const NotchTab& t, float* c, i64 ti
     return launch_notch<1>(P, st, t, c, tile_stride, nlines, es, ls, cnt);
 }
 
+// sosfiltfilt of `lines` lines of n samples per tile.  The group: a chunk of about nine samples per thread, an odd number of them.
+int launch_bleach_filter(const Plan& P, hipStream_t st, const Src& s, int n, int lines, float* F, i64 f_tile_stride, int f_row, float* lmax,
+                         i64 lmax_tile_stride, double* fwd, i64 fwd_tile_stride, int cnt) {
+    const int len = n + 2 * kBleachExt, cap = std::min(len, kBleachSeg);
+    const int threads = std::min(kBleachMaxThreads, std::max(64, (cap / 9 + 63) / 64 * 64));
+    const int chunk = ((cap + threads - 1) / threads) | 1;
+    const size_t lds = (size_t)(cap + (cap & 1)) * sizeof(double) + kBleachTotals;
+    if (lds > 48 * 1024)
+        MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bleach_filter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(bleach_filter_kernel, dim3(lines, cnt), dim3(threads), lds, st, s, n, kBleachSeg, chunk, P.bq, F, f_tile_stride, f_row, lmax,
+                       lmax_tile_stride, len > kBleachSeg ? fwd : nullptr, fwd_tile_stride);
+    return launch_check("bleach_filter_kernel");
+}
+
+// correct_bleaching on the log image behind `L` (the tile through log1p, or the stripe filter's stored result), into the sink
+int run_bleach(Plan& P, hipStream_t st, const Src& L, const Sink& k, int cnt) {
+    const mi_pystripe_info& I = P.info;
+    float* sc = P.scratch.as<float>();
+    const i64 cap = P.cap;
+    auto buf = [&](size_t off) { return sc + (i64)off * cap; };
+    float* M = buf(P.off_M);
+    double* fwd = P.sz_fwd ? reinterpret_cast<double*>(buf(P.off_fwd)) : nullptr;
+    const dim3 grid(cdiv(I.nx, 64), cdiv(I.ny, 4), cnt);
+    if (P.prm.bleach_max_method) {
+        unsigned* key = reinterpret_cast<unsigned*>(buf(P.off_key));
+        float* vec = buf(P.off_vec);
+        const i64 vs = (i64)P.sz_vec;
+        MI_HIP(hipMemsetAsync(key, 0, sizeof(unsigned) * (size_t)vs * (size_t)cnt, st));
+        hipLaunchKernelGGL(bleach_maxima_kernel, dim3(cdiv(I.nx, 64), cdiv(I.ny, 64), cnt), dim3(256), 0, st, L, I.ny, I.nx, key, key + I.ny, vs);
+        MI_TRY(launch_check("bleach_maxima_kernel"));
+        const Src rows{key, vs, SRC_KEY, 1, I.ny, I.ny, 0, MAP_IDENTITY, 0}, cols{key + I.ny, vs, SRC_KEY, 1, I.nx, I.nx, 0, MAP_IDENTITY, 0};
+        MI_TRY(launch_bleach_filter(P, st, rows, I.ny, 1, vec, vs, I.ny, nullptr, 0, fwd, (i64)P.sz_fwd / 2, cnt));
+        MI_TRY(launch_bleach_filter(P, st, cols, I.nx, 1, vec + I.ny, vs, I.nx, nullptr, 0, fwd, (i64)P.sz_fwd / 2, cnt));
+        hipLaunchKernelGGL(bleach_tilemax_kernel, dim3(cnt), dim3(256), 0, st, vec, I.ny, vec + I.ny, I.nx, vs, 1, M);
+        MI_TRY(launch_check("bleach_tilemax_kernel"));
+        hipLaunchKernelGGL(bleach_apply_kernel, grid, dim3(256), 0, st, L, (const float*)nullptr, (i64)0, vec, vec + I.ny, vs, M, k);
+    } else {
+        float* F = buf(P.off_F);
+        float* lmax = buf(P.off_lmax);
+        MI_TRY(launch_bleach_filter(P, st, L, I.nx, I.ny, F, (i64)P.sz_F, I.nx, lmax, (i64)P.sz_lmax, fwd, (i64)P.sz_fwd / 2, cnt));
+        hipLaunchKernelGGL(bleach_tilemax_kernel, dim3(cnt), dim3(256), 0, st, lmax, I.ny, (const float*)nullptr, 0, (i64)P.sz_lmax, 0, M);
+        MI_TRY(launch_check("bleach_tilemax_kernel"));
+        hipLaunchKernelGGL(bleach_apply_kernel, grid, dim3(256), 0, st, L, F, (i64)P.sz_F, (const float*)nullptr, (const float*)nullptr, (i64)0, M, k);
+    }
+    return launch_check("bleach_apply_kernel");
+}
+
 int run_chunk(Plan& P, hipStream_t st, const void* in, const float* flat, void* out, int cnt) {
     const mi_pystripe_info& I = P.info;
     const mi_pystripe_params& q = P.prm;
@@ -641,7 +945,7 @@ int run_chunk(Plan& P, hipStream_t st, const void* in, const float* flat, void* 
     k.out = out;
     k.tile_stride = (i64)I.out_ny * I.out_nx;
     k.ny = I.ny; k.nx = I.nx; k.pad = I.base_pad;
-    k.filtered = P.filter; k.log_out = q.log_output; k.integer_kind = I.integer_kind;
+    k.filtered = P.filter || P.bleach; k.log_out = q.log_output; k.integer_kind = I.integer_kind;
     k.in_max = P.in_dtype == MI_PS_U8 ? 255.f : 65535.f;
     k.dark = q.dark;
     const int cur = I.integer_kind ? P.in_dtype : MI_PS_F32;
@@ -653,9 +957,20 @@ int run_chunk(Plan& P, hipStream_t st, const void* in, const float* flat, void* 
     k.flip = q.flip_upside_down; k.rot = q.rotate / 90;
     k.varies = varies;
     if (!P.filter) {
+        if (P.bleach) {
+            src.logp = 1;   // L is log1p on load: no log image is written
+            return run_bleach(P, st, src, k, cnt);
+        }
         const dim3 grid(cdiv(I.nx, 64), cdiv(I.ny, 4), cnt);
         hipLaunchKernelGGL(point_kernel, grid, dim3(256), 0, st, src, k);
         return launch_check("point_kernel");
+    }
+    // with the bleach correction behind it, the last synthesis level stores the log image; the correction feeds the real sink
+    Sink kL = k;
+    if (P.bleach) {
+        kL.out = buf(P.off_L);
+        kL.tile_stride = (i64)P.sz_L;
+        kL.log_out = 1;
     }
     const int Lv = I.levels;
     for (int pass = 0; pass < P.passes; ++pass) {
@@ -710,16 +1025,18 @@ int run_chunk(Plan& P, hipStream_t st, const void* in, const float* flat, void* 
             const dim3 grid(cdiv(xp1 - xp0, 256), y1 - y0, cnt);
             if (fin) {
                 hipLaunchKernelGGL(syn_rows_kernel<true>, grid, dim3(256), 0, st, buf(P.off_rowL), buf(P.off_rowH), (i64)P.sz_row, m1, y0, xp0, xp1,
-                                   s1, (float*)nullptr, (i64)0, k, P.f);
+                                   s1, (float*)nullptr, (i64)0, kL, P.f);
             } else {
                 float* dst = l == 1 ? buf(P.off_P) : buf(P.off_A[l - 1]);
                 const i64 dst_stride = l == 1 ? (i64)P.sz_P : (i64)P.sz_A[l - 1];
                 hipLaunchKernelGGL(syn_rows_kernel<false>, grid, dim3(256), 0, st, buf(P.off_rowL), buf(P.off_rowH), (i64)P.sz_row, m1, y0, xp0, xp1,
-                                   s1, dst, dst_stride, k, P.f);
+                                   s1, dst, dst_stride, kL, P.f);
             }
             MI_TRY(launch_check("syn_rows_kernel"));
         }
     }
+    if (P.bleach)
+        return run_bleach(P, st, Src{buf(P.off_L), (i64)P.sz_L, MI_PS_F32, I.ny, I.nx, I.nx, 0, MAP_IDENTITY, 0}, k, cnt);
     return MI_OK;
 }
 

@@ -13,6 +13,9 @@ an error.
 What is computed (reference line numbers in include/mi_pystripe.h): uniform tile -> zeros; flat field; ``down_sample`` (max / min /
 mean, zero-padded blocks like skimage's ``block_reduce``); ``filter_streaks`` = log1p, numpy padding (reflect / wrap / symmetric /
 edge), db9 wavelet decomposition, the packed-position Gaussian notch on cH (and cV when ``bidirectional``), reconstruction, crop,
+bleach correction (``bleach_correction_frequency`` with the three clips given, in log1p units: the log-domain image divided by a
+zero-phase first-order Butterworth low-pass of its clipped copy -- row by row, or, with ``bleach_correction_max_method``, the outer
+product of the filtered row and column maxima -- and rescaled by that copy's maximum; it also runs alone, at ``sigma=(0, 0)``),
 expm1, rint + clip for integer tiles; ``dark``; ``lightsheet`` (pystripe/lightsheet_correct.py: local percentiles on two sub-grids,
 order-1 resampling, subtraction; include/mi_lightsheet.h); 8 / 16-bit conversion; flip; rotation.
 
@@ -22,12 +25,14 @@ Departures, all stated in INTEGRATION.md:
   * ``gaussian_filter_2d`` is accepted and does nothing, as in the reference (its GaussianBlur result is discarded);
   * ``lightsheet=True`` on a tile narrower than ``artifact_length`` or with an extent below 25 is refused (the reference returns
     zeros for a uniform such tile and divides by zero otherwise);
-  * refused by name: ``bleach_correction_frequency``, ``enable_masking``, ``exclude_dark_edges_set_them_to_zero``,
+  * refused by name: ``bleach_correction_frequency`` without all three clips (the automatic ones need ``threshold_multiotsu``),
+    ``enable_masking``, ``exclude_dark_edges_set_them_to_zero``,
     ``new_size``, ``.dcimg`` input, ``down_sample_method='median'``, wavelets other than ``db9``, other padding modes, a ``threshold``
     (``use_thresholding`` is never set on this path; ``crossover`` has no effect there either);
   * accepted and ignored: ``workers``, ``threads_per_gpu``, ``timeout``, ``gpu_semaphore``, ``z_step``, ``print_input_file_names``,
     ``verbose``.
-The command line takes the reference's LONG option names with plain ``store_true`` flags; the reference's own parser cannot be built
+The command line takes the reference's LONG option names with plain ``store_true`` flags (the bleach options, which the reference's
+parser lacks, are named after the keywords); the reference's own parser cannot be built
 (``-w`` is given to two options), so the CLI is not claimed as a byte-for-byte drop-in.
 """
 from __future__ import annotations
@@ -112,8 +117,9 @@ def _refuse(name, value, why):
 
 def _check_unsupported(kw):
     """Raises NotImplementedError naming the first option this build does not do."""
-    if kw.get("bleach_correction_frequency") is not None:
-        _refuse("bleach_correction_frequency", kw["bleach_correction_frequency"], "bleach correction is not built")
+    if kw.get("bleach_correction_frequency") is not None and any(kw.get(name) is None for name in BLEACH_CLIPS):
+        _refuse("bleach_correction_frequency", kw["bleach_correction_frequency"],
+                "bleach_correction_clip_min / _med / _max must be given: threshold_multiotsu is not built")
     for name in ("enable_masking", "exclude_dark_edges_set_them_to_zero"):
         if kw.get(name):
             _refuse(name, kw[name], "not built (needs OpenCV / scikit-image semantics)")
@@ -123,6 +129,44 @@ def _check_unsupported(kw):
         _refuse("threshold", kw["threshold"], "the thresholding dual-band path is not built")
     if kw.get("log1p_normalization_needed") is False:
         _refuse("log1p_normalization_needed", False, "only the log1p path is built")
+
+
+BLEACH_CLIPS = ("bleach_correction_clip_min", "bleach_correction_clip_med", "bleach_correction_clip_max")
+_FLOATS = (float, np.float32, np.float64)
+
+
+def check_bleach(shape, frequency, clip_min, clip_med, clip_max, max_method=False, down_sample=None):
+    """What the reference raises for these bleach-correction arguments on a tile of ``shape``, from the values alone: the asserts of
+    correct_bleaching (pystripe/core.py:524-528) as AssertionError, then butter's ValueError for a frequency of 1 or more, then
+    sosfiltfilt's for a filtered line of 6 samples or fewer (the rows; with ``max_method`` also the column of row maxima)."""
+    def require(ok, what):
+        if not ok:
+            raise AssertionError(what)
+    require(isinstance(frequency, _FLOATS) and frequency > 0, f"bleach_correction_frequency={frequency!r}: a float above 0 is expected")
+    require(isinstance(clip_min, _FLOATS) and clip_min >= 0, f"bleach_correction_clip_min={clip_min!r}: a float, 0 or more, is expected")
+    require(isinstance(clip_med, _FLOATS) and clip_med > clip_min,
+            f"bleach_correction_clip_med={clip_med!r}: a float above bleach_correction_clip_min={clip_min!r} is expected")
+    require(isinstance(clip_max, _FLOATS) and clip_max > clip_min,
+            f"bleach_correction_clip_max={clip_max!r}: a float above bleach_correction_clip_min={clip_min!r} is expected")
+    require(clip_max > clip_med, f"bleach_correction_clip_max={clip_max!r} is not above bleach_correction_clip_med={clip_med!r}")
+    if not frequency < 1:
+        raise ValueError(f"Digital filter critical frequencies must be 0 < Wn < 1 (bleach_correction_frequency={frequency!r})")
+    shape = tuple(int(v) for v in shape[-2:])
+    if down_sample is not None:
+        shape = calculate_down_sampled_size(shape, down_sample)
+    for n in (shape if max_method else shape[1:]):
+        if n <= 6:
+            raise ValueError(f"The length of the input vector x must be greater than padlen, which is 6. (bleach correction filters a "
+                             f"line of {n} samples of a tile of shape {shape})")
+
+
+def _bleach_opts(shape, down_sample, frequency, max_method, clip_min, clip_med, clip_max):
+    """{} or the bleach keywords of make_params, after the checks that need no device."""
+    if frequency is None:
+        return {}
+    check_bleach(shape, frequency, clip_min, clip_med, clip_max, max_method, down_sample)
+    return dict(bleach_correction_frequency=frequency, bleach_correction_max_method=max_method, bleach_correction_clip_min=clip_min,
+                bleach_correction_clip_med=clip_med, bleach_correction_clip_max=clip_max)
 
 
 def _sigma_pair(sigma):
@@ -143,7 +187,9 @@ def _dtype_code(dt, what):
 
 def make_params(in_dtype, flat=False, down_sample=None, down_sample_method="max", sigma=(0, 0), level=0, wavelet="db9",
                 padding_mode="reflect", bidirectional=False, dark=0, rotate=0, flip_upside_down=False, convert_to_16bit=False,
-                convert_to_8bit=False, bit_shift_to_right=8, d_type=None, log_output=False, keep_uniform=False, max_batch=0):
+                convert_to_8bit=False, bit_shift_to_right=8, d_type=None, log_output=False, keep_uniform=False, max_batch=0,
+                bleach_correction_frequency=None, bleach_correction_max_method=False, bleach_correction_clip_min=None,
+                bleach_correction_clip_med=None, bleach_correction_clip_max=None):
     """mi_pystripe_params for process_img's options.  Everything the C side cannot name itself is refused here."""
     s1, s2 = _sigma_pair(sigma)
     filt = (s1, s2) > (0, 0)
@@ -193,6 +239,13 @@ def make_params(in_dtype, flat=False, down_sample=None, down_sample_method="max"
         out = in_dtype if d_type is None else d_type
     p.out_dtype = _dtype_code(out, "d_type")
     p.log_output, p.keep_uniform, p.max_batch = int(bool(log_output)), int(bool(keep_uniform)), int(max_batch)
+    if bleach_correction_frequency is not None:
+        clips = dict(bleach_correction_clip_min=bleach_correction_clip_min, bleach_correction_clip_med=bleach_correction_clip_med,
+                     bleach_correction_clip_max=bleach_correction_clip_max)
+        _check_unsupported(dict(clips, bleach_correction_frequency=bleach_correction_frequency))
+        p.bleach_frequency = float(bleach_correction_frequency)
+        p.bleach_clip_min, p.bleach_clip_med, p.bleach_clip_max = (float(clips[name]) for name in BLEACH_CLIPS)
+        p.bleach_max_method = int(bool(bleach_correction_max_method))
     return p
 
 
@@ -532,14 +585,18 @@ def filter_streaks(img, sigma=(250, 250), level=0, wavelet="db9", crossover=10, 
                    log1p_normalization_needed=True, enable_masking=False, close_steps=50, open_steps=500, verbose=False, device=None,
                    log_output=False):
     """pystripe/core.py:982 on the GPU.  ``crossover`` has no effect on this path (as in the reference).  ``log_output=True`` returns
-    the float32 image just before ``expm1`` (an addition, for tests)."""
-    _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, enable_masking=enable_masking, threshold=threshold,
-                            log1p_normalization_needed=log1p_normalization_needed))
+    the float32 image just before ``expm1`` (an addition, for tests).  The bleach correction needs the three clips (log1p units);
+    with ``sigma=(0, 0)`` it runs alone."""
+    _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, bleach_correction_clip_min=bleach_correction_clip_min,
+                            bleach_correction_clip_med=bleach_correction_clip_med, bleach_correction_clip_max=bleach_correction_clip_max,
+                            enable_masking=enable_masking, threshold=threshold, log1p_normalization_needed=log1p_normalization_needed))
     s1, s2 = _sigma_pair(sigma)
-    if s1 == s2 == 0:
+    if s1 == s2 == 0 and bleach_correction_frequency is None:
         return img
+    bleach = _bleach_opts(img.shape, None, bleach_correction_frequency, bleach_correction_max_method, bleach_correction_clip_min,
+                          bleach_correction_clip_med, bleach_correction_clip_max)
     return _run_tiles(img, None, device, sigma=(s1, s2), level=level, wavelet=wavelet, padding_mode=padding_mode, bidirectional=bidirectional,
-                      keep_uniform=True, log_output=log_output)
+                      keep_uniform=True, log_output=log_output, **bleach)
 
 
 def process_img(img, flat=None, gaussian_filter_2d=False, down_sample=None, down_sample_method="max", tile_size=None, new_size=None,
@@ -552,15 +609,19 @@ def process_img(img, flat=None, gaussian_filter_2d=False, down_sample=None, down
     """pystripe/core.py:1190 on the GPU, the reference's keywords and defaults (so ``wavelet`` must be given as 'db9' when ``sigma`` asks
     for the filter).  ``gaussian_filter_2d`` does nothing, as in the reference, whose GaussianBlur result is discarded.  ``img`` may be
     a stack [n, ny, nx] of equally shaped tiles (an addition): they go through every launch together.  ``lightsheet=True`` runs
-    ``correct_lightsheet`` after ``dark`` as the reference does; a tile too small for one window is refused from its shape alone."""
-    _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, new_size=new_size,
-                            exclude_dark_edges_set_them_to_zero=exclude_dark_edges_set_them_to_zero, threshold=threshold,
+    ``correct_lightsheet`` after ``dark`` as the reference does; a tile too small for one window is refused from its shape alone.
+    ``bleach_correction_frequency`` needs the three clips, in log1p units (the automatic ones are not built)."""
+    _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, bleach_correction_clip_min=bleach_correction_clip_min,
+                            bleach_correction_clip_med=bleach_correction_clip_med, bleach_correction_clip_max=bleach_correction_clip_max,
+                            new_size=new_size, exclude_dark_edges_set_them_to_zero=exclude_dark_edges_set_them_to_zero, threshold=threshold,
                             log1p_normalization_needed=log1p_normalization_needed))
     ls = _lightsheet_opts(lightsheet, img.shape, down_sample, artifact_length, background_window_size, percentile, lightsheet_vs_background)
+    bleach = _bleach_opts(img.shape, down_sample, bleach_correction_frequency, bleach_correction_max_method, bleach_correction_clip_min,
+                          bleach_correction_clip_med, bleach_correction_clip_max)
     return _run_tiles(img, flat, device, lightsheet=ls, down_sample=down_sample, down_sample_method=down_sample_method, sigma=sigma, level=level,
                       wavelet=wavelet, padding_mode=padding_mode, bidirectional=bidirectional, dark=dark, rotate=rotate,
                       flip_upside_down=flip_upside_down, convert_to_16bit=convert_to_16bit, convert_to_8bit=convert_to_8bit,
-                      bit_shift_to_right=bit_shift_to_right, d_type=d_type)
+                      bit_shift_to_right=bit_shift_to_right, d_type=d_type, **bleach)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -660,13 +721,19 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
     batch is read and the previous one written on host threads while the device works on the current one.  Under ``torchrun`` every
     rank takes every WORLD_SIZE-th file on its LOCAL_RANK device.  ``continue_process``: a file whose output exists is skipped.  A file
     that cannot be read becomes a zero tile when ``d_type`` and ``tile_size`` are given, else it is skipped with a warning.
-    ``workers``, ``threads_per_gpu``, ``timeout``, ``z_step``, ``print_input_file_names`` are accepted and ignored.  ``stats`` (a dict)
+    ``bleach_correction_frequency`` needs the three clips, in log1p units; ``bleach_correction_max_method`` defaults to True here, as
+    in the reference.  ``workers``, ``threads_per_gpu``, ``timeout``, ``z_step``, ``print_input_file_names`` are accepted and ignored.  ``stats`` (a dict)
     receives the seconds spent reading, computing and writing and the file counts."""
     import time
     import torch
     if convert_to_16bit and convert_to_8bit:
         raise TypeError("convert_to_16bit and convert_to_8bit are both set: choose one output format")
-    _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, new_size=new_size, threshold=threshold))
+    _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, bleach_correction_clip_min=bleach_correction_clip_min,
+                            bleach_correction_clip_med=bleach_correction_clip_med, bleach_correction_clip_max=bleach_correction_clip_max,
+                            new_size=new_size, threshold=threshold))
+    bleach_args = (bleach_correction_frequency, bleach_correction_max_method, bleach_correction_clip_min, bleach_correction_clip_med,
+                   bleach_correction_clip_max)
+    _bleach_opts((7, 7), None, *bleach_args)   # the values alone; every tile shape is checked when it is met
     input_path, output_path = Path(input_path), Path(output_path)
     if input_path.suffix.lower() == ".dcimg":
         _refuse("input_path", str(input_path), ".dcimg input is not built")
@@ -687,7 +754,8 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
         tile_size = tuple(int(v) for v in tile_size)
     opts = dict(down_sample=down_sample, down_sample_method=down_sample_method, sigma=sigma, level=level, wavelet=wavelet,
                 padding_mode=padding_mode, bidirectional=bidirectional, dark=dark, rotate=rotate, flip_upside_down=flip_upside_down,
-                convert_to_16bit=convert_to_16bit, convert_to_8bit=convert_to_8bit, bit_shift_to_right=bit_shift_to_right, d_type=d_type)
+                convert_to_16bit=convert_to_16bit, convert_to_8bit=convert_to_8bit, bit_shift_to_right=bit_shift_to_right, d_type=d_type,
+                **_bleach_opts((7, 7), None, *bleach_args))
 
     st = dict(read_s=0.0, compute_s=0.0, write_s=0.0, files=len(files), written=0, skipped_existing=0, skipped_unreadable=0, zero_tiles=0)
     todo = []
@@ -766,6 +834,7 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
                 print("warning: image and flat arrays had different shapes")
             key = (shape, dt, use_flat)
             if key not in plans:
+                _bleach_opts(shape, down_sample, *bleach_args)
                 ls = _lightsheet_opts(lightsheet, shape, down_sample, artifact_length, background_window_size, percentile,
                                       lightsheet_vs_background)
                 plans[key] = (Pipeline(device, shape, dt, flat=use_flat, lightsheet=ls, max_batch=chunk, **opts),
@@ -784,6 +853,7 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
     elif todo:
         first = imread_tif_raw_png(todo[0][0]) if tile_size is None else np.zeros(tile_size, np.dtype(d_type or np.uint16))
         if first is not None and first.ndim == 2 and first.dtype in _NP_CODES:
+            _bleach_opts(first.shape, down_sample, *bleach_args)
             info = derive(first.shape, first.dtype, make_params(first.dtype, flat=False, **opts))
             per_tile = info.scratch_bytes_per_tile + 2 * first.size * 4
             with torch.cuda.device(device):
@@ -850,6 +920,14 @@ def _parse_args(argv=None):
     p.add_argument("--tile_size", type=int, nargs=2, default=None, metavar=("NY", "NX"))
     p.add_argument("--gaussian_filter_2d", action="store_true", help="accepted; does nothing, as in the reference")
     p.add_argument("--max_batch", type=int, default=None, help="tiles per launch (default: from the free device memory)")
+    p.add_argument("--bleach_correction_frequency", type=float, default=None,
+                   help="bleach correction: cutoff of the low-pass as a fraction of the Nyquist frequency, in (0, 1); 1 / tile size is usual")
+    for name, what in (("min", "background vs foreground threshold"), ("med", "intermediate foreground value (it also replaces exact zeros)"),
+                       ("max", "largest foreground value")):
+        p.add_argument(f"--bleach_correction_clip_{name}", type=float, default=None,
+                       help=f"bleach correction: {what}, in log1p units (log1p of the intensity); all three clips are required")
+    p.add_argument("--bleach_correction_max_method", action=argparse.BooleanOptionalAction, default=True,
+                   help="bleach correction from the filtered row and column maxima (default) rather than from every filtered row")
     return p.parse_args(argv)
 
 
@@ -865,7 +943,9 @@ def main(argv=None):
     stats = {}
     rc = batch_filter(inp, out, flat=flat, gaussian_filter_2d=a.gaussian_filter_2d, sigma=(a.sigma1, a.sigma2), level=a.level,
                       wavelet=a.wavelet, crossover=a.crossover, threshold=a.threshold, padding_mode=a.padding_mode,
-                      bidirectional=a.bidirectional, dark=a.dark, rotate=a.rotate, flip_upside_down=a.flip_upside_down,
+                      bidirectional=a.bidirectional, bleach_correction_frequency=a.bleach_correction_frequency,
+                      bleach_correction_max_method=a.bleach_correction_max_method, bleach_correction_clip_min=a.bleach_correction_clip_min,
+                      bleach_correction_clip_med=a.bleach_correction_clip_med, bleach_correction_clip_max=a.bleach_correction_clip_max, dark=a.dark, rotate=a.rotate, flip_upside_down=a.flip_upside_down,
                       lightsheet=a.lightsheet, artifact_length=a.artifact_length, background_window_size=a.background_window_size,
                       percentile=a.percentile, lightsheet_vs_background=a.lightsheet_vs_background, convert_to_16bit=a.convert_to_16bit, convert_to_8bit=a.convert_to_8bit,
                       bit_shift_to_right=a.bit_shift_to_right, continue_process=a.continue_process, d_type=a.dtype,

@@ -3,7 +3,9 @@
  *
  * Replaces, for the options process_images.py uses, pystripe/core.py:
  *   process_img            :1190-1381  (uniform tile, flat, down_sample, filter_streaks, dark, 8/16-bit conversion, flip, rotate)
- *   filter_streaks         :982-1159   (log1p, padding, filter_streak_dual_band, crop, expm1, rint + clip for integer tiles)
+ *   filter_streaks         :982-1159   (log1p, padding, filter_streak_dual_band, crop, bleach correction, expm1, rint + clip for
+ *                                       integer tiles)
+ *   correct_bleaching      :501-559, butter_lowpass_filter :492-498  (with explicit clips; see "Bleach correction" below)
  *   filter_streak_dual_band:943-979    (sigma1 == sigma2: one filter_subband; else one after the other)
  *   filter_subband         :927-940    (numpy branch: wavedec2 'symmetric' db9, np_filter_coefficient on cH and cV, waverec2)
  *   np_filter_coefficient  :749-754, np_notch :637-667  (gains applied by PACKED position of scipy.fftpack.rfft's real spectrum)
@@ -11,9 +13,23 @@
  *   is_uniform_2d          :107-121,  calculate_down_sampled_size :1162-1170
  * skimage.measure.block_reduce (zero padding to a multiple of the block) is restated for max / min / mean.
  *
- * Not built (refused by the Python layer by name): bleach correction, masking, dark-edge exclusion, new_size, wavelets other than
- * db9, padding modes other than reflect / wrap / symmetric / edge, the median down-sampling.  The lightsheet correction of
- * process_img :1333-1348 is mi_lightsheet.h; the Python layer runs it between two plans of this header.
+ * Not built (refused by the Python layer by name): the automatic bleach-correction clips (threshold_multiotsu), masking, dark-edge
+ * exclusion, new_size, wavelets other than db9, padding modes other than reflect / wrap / symmetric / edge, the median
+ * down-sampling.  The lightsheet correction of process_img :1333-1348 is mi_lightsheet.h; the Python layer runs it between two
+ * plans of this header.
+ *
+ * Bleach correction (bleach_frequency > 0), on the float32 log-domain image L (the stripe filter's cropped result, or log1p(tile)
+ * when sigma == (0, 0)), just before expm1:
+ *   G  = L with exact zeros replaced by clip_med, limited to [max(clip_min, log1p(1)), clip_max] (the bounds as float32);
+ *   F  = every row of G through scipy's sosfiltfilt(butter(1, frequency, 'sos'), .) in float64, stored as float32: the row is
+ *        extended by 6 samples per side (odd extension), then y[i] = b u[i] + z, z = b u[i] + a y[i] runs forward from
+ *        z = (1 - b) u[0] and once more backward over the result, with k = tan(pi frequency / 2), b = k / (1 + k),
+ *        a = (1 - k) / (1 + k);
+ *        max_method: the row maxima and column maxima of L go through the same clip and filter over their own length, and
+ *        F[y][x] = ry[y] * cx[x] (a float32 product, never stored);
+ *   L' = (L / F) * max(F) in float32, the maximum over the tile; then the tail as before.
+ * A row (or maxima vector) of n samples stays in LDS as n + 12 doubles while n <= MI_PS_BLEACH_LDS_ROW; a longer one goes through
+ * LDS in segments with the carried filter state and a float64 scratch row for the forward result.
  */
 #ifndef MI_PYSTRIPE_H
 #define MI_PYSTRIPE_H
@@ -28,6 +44,9 @@ typedef enum { MI_PS_U8 = 0, MI_PS_U16 = 1, MI_PS_F32 = 2 } mi_pystripe_dtype;
 typedef enum { MI_PS_REFLECT = 0, MI_PS_WRAP = 1, MI_PS_SYMMETRIC = 2, MI_PS_EDGE = 3 } mi_pystripe_padding;   /* numpy.pad modes */
 typedef enum { MI_PS_DOWN_MAX = 0, MI_PS_DOWN_MIN = 1, MI_PS_DOWN_MEAN = 2 } mi_pystripe_down;
 #define MI_PS_MAX_LEVELS 24
+/* bleach correction: the longest row whose n + 12 doubles fit the LDS of one work-group beside the 16 wave totals of the scan:
+ * (160 KiB - 16 * 16 B) / 8 B - 12 */
+#define MI_PS_BLEACH_LDS_ROW 20436
 
 typedef struct {
     double sigma1, sigma2;     /* (0, 0): no stripe filter; both > 0 otherwise ("sigma must be positive", np_notch :654) */
@@ -44,9 +63,13 @@ typedef struct {
     int out_dtype;             /* mi_pystripe_dtype of the result (d_type; uint16 / uint8 when a conversion flag is set) */
     int flip_upside_down;
     int rotate;                /* 0, 90, 180, 270: numpy.rot90(img, rotate / 90) after the flip */
-    int log_output;            /* 1: float32 output of the filtered image BEFORE expm1 (cropped, nothing after it applied) */
+    int log_output;            /* 1: float32 output of the log-domain image BEFORE expm1 (cropped, nothing after it applied): the stripe
+                                  filter's result, after the bleach correction when that is on; needs one of the two */
     int max_batch;             /* tiles that go through one launch (scratch is held for this many); <= 0: 16 */
     int keep_uniform;          /* 1: no uniform-tile rule (filter_streaks called on its own filters a uniform tile like any other) */
+    double bleach_frequency;   /* 0: no bleach correction; else butter's Wn, in (0, 1) (1: the Nyquist frequency) */
+    double bleach_clip_min, bleach_clip_med, bleach_clip_max;   /* log1p units: 0 <= min < med < max; min is raised to log1p(1) */
+    int bleach_max_method;     /* 1: F is the outer product of the filtered row and column maxima of L */
 } mi_pystripe_params;
 
 typedef struct {
@@ -59,6 +82,7 @@ typedef struct {
     int integer_kind;          /* 1: the tile is an integer tile inside process_img (rint + clip after expm1, truncating dark) */
     int max_batch;
     size_t scratch_bytes_per_tile;
+    int bleach_long_rows;      /* 1: a filtered line of the bleach correction is longer than MI_PS_BLEACH_LDS_ROW (segmented route) */
 } mi_pystripe_info;
 
 /* A plan for tiles of ny x nx samples of in_dtype on device dev.  Synchronises (uploads its tables).  A plan owns its scratch:
