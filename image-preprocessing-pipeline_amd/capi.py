@@ -23,6 +23,8 @@ HALVE_MEAN, HALVE_MAX = 0, 1   # mi_halve_method (include/mi_pyramid.h)
 PS_U8, PS_U16, PS_F32 = 0, 1, 2   # mi_pystripe_dtype (include/mi_pystripe.h)
 PS_PADDING = {"reflect": 0, "wrap": 1, "symmetric": 2, "edge": 3}   # mi_pystripe_padding
 PS_DOWN = {"max": 0, "min": 1, "mean": 2}   # mi_pystripe_down
+CODES_U8, CODES_U16 = 0, 1   # mi_code_dtype (include/mi_thresholds.h)
+OTSU_OK, OTSU_TOO_FEW_VALUES, OTSU_VALUES_ARE_CLASSES = 0, 1, 2   # mi_otsu_status
 
 
 MI_ERR_INVALID, MI_ERR_HIP, MI_ERR_FFT, MI_ERR_NOMEM, MI_ERR_UNSUPPORTED = -1, -2, -3, -4, -5  # include/mi_common.h
@@ -233,6 +235,10 @@ SIGNATURES = {
     "mi_isodown_run": (_i, [_vp, _vp, _vp, C.c_int64, _vp, _vp]),
     "mi_isodown_reduce_z": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "mi_resize_antialias": (_i, [_i, _vp, _vp, _i, _ip, _ip, _vp]),
+    # mi_thresholds.h
+    "mi_hist256_f32": (_i, [_i, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp, _vp]),
+    "mi_code_hist": (_i, [_i, _vp, _vp, _i, _i, C.c_int64, _vp]),
+    "mi_multiotsu_search": (_i, [_i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     # mi_crossmips.h
     "mi_ncc_default_params": (None, [_i, _i, _i, C.POINTER(NccParams)]),
     "mi_ncc_mips": (_i, [_i, _vp, _vp, _vp] + [_i] * 10 + [C.POINTER(NccParams), C.POINTER(NccDescr)]),

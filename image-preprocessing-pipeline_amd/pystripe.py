@@ -925,10 +925,28 @@ def _parse_args(argv=None):
     for name, what in (("min", "background vs foreground threshold"), ("med", "intermediate foreground value (it also replaces exact zeros)"),
                        ("max", "largest foreground value")):
         p.add_argument(f"--bleach_correction_clip_{name}", type=float, default=None,
-                       help=f"bleach correction: {what}, in log1p units (log1p of the intensity); all three clips are required")
+                       help=f"bleach correction: {what}, in log1p units (log1p of the intensity); all three clips are required unless --estimate_clips fills them")
     p.add_argument("--bleach_correction_max_method", action=argparse.BooleanOptionalAction, default=True,
                    help="bleach correction from the filtered row and column maxima (default) rather than from every filtered row")
-    return p.parse_args(argv)
+    p.add_argument("--estimate_clips", action="store_true",
+                   help="with --bleach_correction_frequency: take the clips that are not given from the slices of --input at 25 %%, 50 %% and "
+                        "75 %% of the depth (four-class multi-Otsu of the log1p image, as process_images.py does) and print them")
+    a = p.parse_args(argv)
+    if a.estimate_clips and a.bleach_correction_frequency is None:
+        p.error("--estimate_clips fills the bleach-correction clips: --bleach_correction_frequency must be given")
+    return a
+
+
+def _estimated_clips(a, estimate=None):
+    """The three clips of the command line; with --estimate_clips those not given come from ``estimate_slice_params`` on --input."""
+    clips = {name: getattr(a, name) for name in BLEACH_CLIPS}
+    if a.estimate_clips and any(v is None for v in clips.values()):
+        if estimate is None:
+            from .thresholds import estimate_slice_params as estimate
+        found = estimate(a.input, need_bleach_correction=True, need_16bit_to_8bit_conversion=False)
+        clips = {name: found[name] if value is None else value for name, value in clips.items()}
+        print("pystripe: " + ", ".join(f"--{name}={value!r}" for name, value in clips.items()))
+    return clips
 
 
 def main(argv=None):
@@ -940,18 +958,18 @@ def main(argv=None):
         flat = imread_tif_raw_png(Path(a.flat))
         if flat is None:
             raise SystemExit(f"--flat={a.flat}: cannot be read")
+    clips = _estimated_clips(a)
     stats = {}
     rc = batch_filter(inp, out, flat=flat, gaussian_filter_2d=a.gaussian_filter_2d, sigma=(a.sigma1, a.sigma2), level=a.level,
                       wavelet=a.wavelet, crossover=a.crossover, threshold=a.threshold, padding_mode=a.padding_mode,
                       bidirectional=a.bidirectional, bleach_correction_frequency=a.bleach_correction_frequency,
-                      bleach_correction_max_method=a.bleach_correction_max_method, bleach_correction_clip_min=a.bleach_correction_clip_min,
-                      bleach_correction_clip_med=a.bleach_correction_clip_med, bleach_correction_clip_max=a.bleach_correction_clip_max, dark=a.dark, rotate=a.rotate, flip_upside_down=a.flip_upside_down,
+                      bleach_correction_max_method=a.bleach_correction_max_method, dark=a.dark, rotate=a.rotate, flip_upside_down=a.flip_upside_down,
                       lightsheet=a.lightsheet, artifact_length=a.artifact_length, background_window_size=a.background_window_size,
                       percentile=a.percentile, lightsheet_vs_background=a.lightsheet_vs_background, convert_to_16bit=a.convert_to_16bit, convert_to_8bit=a.convert_to_8bit,
                       bit_shift_to_right=a.bit_shift_to_right, continue_process=a.continue_process, d_type=a.dtype,
                       tile_size=tuple(a.tile_size) if a.tile_size else None, down_sample=tuple(a.down_sample) if a.down_sample else None,
                       down_sample_method=a.down_sample_method, compression=(a.compression_method, a.compression_level),
-                      max_batch=a.max_batch, stats=stats)
+                      max_batch=a.max_batch, stats=stats, **clips)
     print("pystripe: {files} files, {written} written, {skipped_existing} already there, {skipped_unreadable} unreadable, "
           "{zero_tiles} zero tiles; read {read_s:.2f} s, compute {compute_s:.2f} s, write {write_s:.2f} s".format(**stats))
     return rc
