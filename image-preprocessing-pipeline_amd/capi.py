@@ -120,6 +120,24 @@ class IsodownInfo(C.Structure):
                 ("taps_x", C.c_int), ("tile_ny", C.c_int), ("tile_nx", C.c_int), ("lds_steps", C.c_int), ("scratch_bytes_per_slice", C.c_size_t)]
 
 
+ECC_NSUMS, ECC_SCRATCH_BYTES, ECC_DEFAULT_BATCH = 16, 1024 * 16 * 8, 32   # MI_ECC_NSUMS, MI_ECC_SCRATCH_BYTES, MI_ECC_DEFAULT_BATCH
+ECC_OK, ECC_NAN, ECC_MINIMIZED = 0, 1, 2   # mi_ecc_status
+ECC_SUM_NAMES = ("n", "sw", "sww", "st", "stt", "swt", "hxx", "hxy", "hyy", "gxw", "gyw", "mgx", "mgy", "gxt", "gyt")   # mi_ecc_sum
+RGB_U8, RGB_U16, RGB_U32, RGB_F32 = 1, 2, 3, 4   # mi_rgb_dtype; also the dtype of mi_tiff_write_rgb_series
+
+
+class EccState(C.Structure):
+    """mi_ecc_state (include/mi_align.h)."""
+    _fields_ = [("tx", C.c_double), ("ty", C.c_double), ("rho", C.c_double), ("rho_last", C.c_double), ("iteration", C.c_int),
+                ("status", C.c_int), ("done", C.c_int), ("reserved", C.c_int)]
+
+
+class CompositeChannel(C.Structure):
+    """mi_composite_channel (include/mi_align.h)."""
+    _fields_ = [("src", C.c_void_p), ("count", C.c_int), ("first", C.c_int), ("ny", C.c_int), ("nx", C.c_int), ("dz", C.c_int),
+                ("dy", C.c_int), ("dx", C.c_int), ("reserved", C.c_int)]
+
+
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _ip = C.POINTER(C.c_int)
 
@@ -193,7 +211,8 @@ SIGNATURES = {
     "mi_tiff_info": (_i, [C.c_char_p, _ip, _ip, _ip, _ip]),
     "mi_tiff_read_box": (_i, [C.POINTER(C.c_char_p), _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i]),
     "mi_tiff_write_series": (_i, [C.POINTER(C.c_char_p), _i, _vp, _i, _i, _i, _i, _i, _i, _ip]),
-    "mi_tiff_write_series_device": (_i, [_i, _vp, C.POINTER(C.c_char_p), _i, _vp, _i, _i, _i, _i, _ip]),
+    "mi_tiff_write_rgb_series": (_i, [C.POINTER(C.c_char_p), _i, _vp, _i, _i, _i, _i, _i, _i, _ip]),
+    "mi_tiff_write_series_device":(_i, [_i, _vp, C.POINTER(C.c_char_p), _i, _vp, _i, _i, _i, _i, _ip]),
     "mi_peer_link_create": (_i, [_i, _sz, C.POINTER(_vp), C.c_char_p, C.c_char_p]),
     "mi_peer_link_connect": (_i, [_vp, _i, C.c_char_p, C.c_char_p, _i]),
     "mi_peer_link_begin": (_i, [_vp, _vp, C.c_uint, _i]),
@@ -239,6 +258,13 @@ SIGNATURES = {
     "mi_hist256_f32": (_i, [_i, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp, _vp]),
     "mi_code_hist": (_i, [_i, _vp, _vp, _i, _i, C.c_int64, _vp]),
     "mi_multiotsu_search": (_i, [_i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    # mi_align.h
+    "mi_sobel2d_f32": (_i, [_i, _vp, _vp, _i, _i, _vp]),
+    "mi_ecc_prepare": (_i, [_i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "mi_ecc_sums": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, _vp, _vp]),
+    "mi_ecc_translation_run": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, _i, C.c_double, _i, _vp, _vp,
+                                    C.POINTER(EccState)]),
+    "mi_channel_composite": (_i, [_i, _vp, C.POINTER(CompositeChannel), _i, _i, _i, _i, _i, _vp, _i]),
     # mi_crossmips.h
     "mi_ncc_default_params": (None, [_i, _i, _i, C.POINTER(NccParams)]),
     "mi_ncc_mips": (_i, [_i, _vp, _vp, _vp] + [_i] * 10 + [C.POINTER(NccParams), C.POINTER(NccDescr)]),

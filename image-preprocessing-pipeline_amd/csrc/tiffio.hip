@@ -385,6 +385,69 @@ std::string write_slice(const char* path, const char* data, int nx, int ny, int 
     return finish_file(path, file, off, cnt, nx, ny, dtype, compression, rps);
 }
 
+// The RGB series of align_images.py: header | strips | strip tables | BitsPerSample and SampleFormat triples | directory.
+// bps: bytes per sample; format: 1 unsigned integer, 3 IEEE float.  Rows hold nx pixels of three samples each (chunky).
+std::string write_rgb_slice(const char* path, const char* data, int nx, int ny, size_t bps, uint32_t format, int compression, Zip& zp,
+                            std::vector<unsigned char>& file) {
+    const size_t rowb = (size_t)nx * 3 * bps;
+    const uint32_t rps = (uint32_t)std::max<size_t>(1, std::min<size_t>((size_t)ny, ((size_t)1 << 20) / std::max<size_t>(1, rowb)));
+    const uint32_t ns = ((uint32_t)ny + rps - 1) / rps;
+    std::vector<uint32_t> off(ns), cnt(ns);
+    file.clear();
+    file.reserve((size_t)ny * rowb / (compression ? 2 : 1) + 4096);
+    file.resize(8);
+    for (uint32_t s = 0; s < ns; ++s) {
+        const uint32_t r0 = s * rps, r1 = std::min<uint32_t>((uint32_t)ny, r0 + rps);
+        const size_t n = (size_t)(r1 - r0) * rowb, at = file.size();
+        if (compression) {
+            const size_t cap = zp.bound(n);
+            file.resize(at + cap);
+            const size_t got = zp.pack(data + (size_t)r0 * rowb, n, file.data() + at, cap);
+            if (!got) return std::string(path) + ": deflate failed";
+            file.resize(at + got);
+            cnt[s] = (uint32_t)got;
+        } else {
+            file.insert(file.end(), reinterpret_cast<const unsigned char*>(data) + (size_t)r0 * rowb,
+                        reinterpret_cast<const unsigned char*>(data) + (size_t)r0 * rowb + n);
+            cnt[s] = (uint32_t)n;
+        }
+        off[s] = (uint32_t)at;
+        if (file.size() & 1) file.push_back(0);
+        if (file.size() > 0xfff00000ull) return std::string(path) + ": a slice of more than 4 GB needs BigTIFF";
+    }
+    uint32_t off_tab = 0, cnt_tab = 0;
+    if (ns > 1) {
+        off_tab = (uint32_t)file.size();
+        for (uint32_t v : off) put32(file, v);
+        cnt_tab = (uint32_t)file.size();
+        for (uint32_t v : cnt) put32(file, v);
+    }
+    const uint32_t bits_at = (uint32_t)file.size();
+    for (int k = 0; k < 3; ++k) put16(file, (uint32_t)(8 * bps));
+    const uint32_t format_at = (uint32_t)file.size();
+    for (int k = 0; k < 3; ++k) put16(file, format);
+    const uint32_t ifd = (uint32_t)file.size();
+    struct Ent { uint16_t tag, type; uint32_t count, value; };
+    const Ent ents[] = {
+        {256, 4, 1, (uint32_t)nx}, {257, 4, 1, (uint32_t)ny}, {258, 3, 3, bits_at}, {259, 3, 1, compression ? 8u : 1u}, {262, 3, 1, 2u},
+        {273, 4, ns, ns > 1 ? off_tab : off[0]}, {277, 3, 1, 3u}, {278, 4, 1, rps}, {279, 4, ns, ns > 1 ? cnt_tab : cnt[0]}, {284, 3, 1, 1u},
+        {339, 3, 3, format_at},
+    };
+    put16(file, (uint32_t)(sizeof ents / sizeof ents[0]));
+    for (const Ent& e : ents) { put16(file, e.tag); put16(file, e.type); put32(file, e.count); put32(file, e.value); }
+    put32(file, 0);
+    file[0] = 'I'; file[1] = 'I'; file[2] = 42; file[3] = 0;
+    file[4] = (unsigned char)(ifd & 255); file[5] = (unsigned char)(ifd >> 8 & 255); file[6] = (unsigned char)(ifd >> 16 & 255); file[7] = (unsigned char)(ifd >> 24);
+    const std::string tmp = std::string(path) + ".tmp";
+    const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+    if (fd < 0) return tmp + ": " + std::strerror(errno);
+    const bool ok = write_all(fd, file.data(), file.size());
+    const int ce = close(fd);
+    if (!ok || ce != 0) { unlink(tmp.c_str()); return tmp + ": write failed: " + std::strerror(errno); }
+    if (rename(tmp.c_str(), path) != 0) { unlink(tmp.c_str()); return std::string(path) + ": " + std::strerror(errno); }
+    return "";
+}
+
 // ------------------------------------------------------------------------------------------------ deflate on the device
 // The writer above spends the host's cores on deflate: 2.7 GB/s on the 16 CPUs of a one-GPU container, while the slab it writes was
 // computed on the device in a fraction of that time.  mi_tiff_write_series_device compresses where the samples are: every strip
@@ -767,6 +830,34 @@ extern "C" int mi_tiff_write_series(const char* const* paths, int nz, const void
         if (!zp[(size_t)t]) zp[(size_t)t] = new Zip(level);
         std::string e = write_slice(paths[k], static_cast<const char*>(vol) + (size_t)k * slice_bytes, nx, ny, dtype, compression, *zp[(size_t)t],
                                     buf[(size_t)t]);
+        if (e.empty()) made.fetch_add(1);
+        return e;
+    });
+    for (Zip* z : zp) delete z;
+    if (written) *written = made.load();
+    return rc;
+}
+
+extern "C" int mi_tiff_write_rgb_series(const char* const* paths, int nz, const void* vol, int dtype, int nx, int ny, int compression, int level,
+                                        int n_threads, int* written) {
+    MI_REQUIRE(paths && vol, "mi_tiff_write_rgb_series: null pointer");
+    MI_REQUIRE(nz >= 0 && nx > 0 && ny > 0 && dtype >= 1 && dtype <= 4, "mi_tiff_write_rgb_series: invalid extents or sample type");
+    MI_REQUIRE((compression == 0 || compression == 1) && level >= 1 && level <= 9, "mi_tiff_write_rgb_series: compression 0 / 1, level 1 .. 9");
+    if (written) *written = 0;
+    if (nz == 0) return MI_OK;
+    const int nt = thread_count(n_threads, nz);
+    const size_t bps = dtype == 1 ? 1 : dtype == 2 ? 2 : 4;
+    const uint32_t format = dtype == 4 ? 3u : 1u;
+    const size_t slice_bytes = (size_t)nx * ny * 3 * bps;
+    std::vector<Zip*> zp((size_t)nt, nullptr);
+    std::vector<std::vector<unsigned char>> buf((size_t)nt);
+    std::atomic<int> made{0};
+    const int rc = run_jobs(nz, nt, [&](int k, int t) -> std::string {
+        struct stat st;
+        if (stat(paths[k], &st) == 0) return "";  // as mi_tiff_write_series: files that exist are kept
+        if (!zp[(size_t)t]) zp[(size_t)t] = new Zip(level);
+        std::string e = write_rgb_slice(paths[k], static_cast<const char*>(vol) + (size_t)k * slice_bytes, nx, ny, bps, format, compression,
+                                        *zp[(size_t)t], buf[(size_t)t]);
         if (e.empty()) made.fetch_add(1);
         return e;
     });

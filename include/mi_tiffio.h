@@ -44,6 +44,15 @@ int mi_tiff_write_series(const char* const* paths, int nz, const void* vol, int 
 int mi_tiff_write_series_device(int dev, void* stream, const char* const* paths, int nz, const void* vol, int dtype, int nx, int ny,
                                 int n_threads, int* written);
 
+/* One RGB file per z slice of vol [nz][ny][nx][3] (host memory), the `RGB` series of align_images.py: classic little-endian TIFF,
+ * SamplesPerPixel 3, PhotometricInterpretation 2 (RGB), PlanarConfiguration 1 (chunky), strips, SampleFormat per type.
+ * dtype: 1 = uint8, 2 = uint16, 3 = uint32, 4 = float32.  compression: 0 none (what the reference's imwrite writes), 1 Adobe deflate
+ * at `level` (1 .. 9).  As with mi_tiff_write_series, a file is written under a temporary name and renamed, and a path that exists
+ * is left alone; *written (may be NULL) counts the files produced.  mi_tiff_info reports such files as not fast.
+ * [align_images.py:51-63 and :322-328: imwrite(path, composite.astype(dtype))] */
+int mi_tiff_write_rgb_series(const char* const* paths, int nz, const void* vol, int dtype, int nx, int ny, int compression, int level,
+                             int n_threads, int* written);
+
 /* Name of the deflate implementation in use: "libdeflate" when libdeflate.so.0 could be loaded, else "zlib". */
 const char* mi_tiff_codec(void);
 
