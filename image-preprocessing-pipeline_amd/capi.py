@@ -225,6 +225,9 @@ SIGNATURES = {
     # mi_stitch.h
     "mi_merge_volume_dims": (_i, [_i, _i, _ip, _ip, _ip, _i, _i, _i, _ip]),
     "mi_merge_slab": (_i, [_i, _vp, _i, _i, _ip, _ip, _ip, _i, _i, _i, C.POINTER(_vp), _i, _i] + [_i] * 6 + [_vp]),
+    # mi_tsv.h
+    "mi_tsv_place": (_i, [_i, _i, _ip, _ip, _i, _ip, _i, _i, _ip, _ip, _ip, _ip]),
+    "mi_tsv_merge": (_i, [_i, _vp, _i, _ip, _ip, _ip, _ip, _i, _i, C.POINTER(_vp), _i, _i] + [_i] * 6 + [_vp]),
     # mi_pyramid.h
     "mi_pyramid_slab": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _ip, C.POINTER(_vp)]),
     "mi_tiff3d_write_blocks": (_i, [_i, C.POINTER(C.c_char_p), C.POINTER(_vp), C.POINTER(C.c_int64), _ip, _ip, _ip, _i, _i, _i, _i,

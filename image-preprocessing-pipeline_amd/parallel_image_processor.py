@@ -1,16 +1,19 @@
 """parallel_image_processor.py on the MI355X: the per-slice pass of the pipeline (``fun`` on every slice of a folder, rotation, the
 full-resolution TIFFs) and its isotropic down-sampled volume (the plane of every z group, ``<name>_zyx<target>um.npz``).
 
-    python parallel_image_processor.py --input DIR --output DIR --voxel_size Z Y X --voxel_size_target T
+    python parallel_image_processor.py --input DIR|PROJECT.xml --output DIR --voxel_size Z Y X --voxel_size_target T
            [--downsampled_path DIR --rotation 0|90|180|270 --down_sampled_dtype float32|uint16|uint8 --no-alternating --rename]
+           [--alt_stack_dir DIR --cosine_blending --ignore_z_offsets]      (with a project XML: the TSVVolume of ipp_amd.tsv)
 
 The down-sampling runs on the device (include/mi_isodown.h): a slice is read there once by the halving kernel, which leaves a plane
 some hundred times smaller; resize, z reduction and the final 3-D resize work on those.  When ``fun`` is
 ``ipp_amd.pystripe.process_img`` a whole z group goes through it as one device stack and stays on the device for rotation and
 down-sampling; only the full-resolution result comes back, for writing.  Any other callable is called per slice on numpy arrays.
+A ``source`` that is an ``ipp_amd.tsv.TSVVolume`` is merged on the device (``imread_device``, one call per z group with
+``process_img``): the stitched planes never exist on the host or on disk before ``fun``.
 
 Built to the restatement of DESIGN section 14 (scikit-image's resize / block_reduce / resize_local_mean written against scipy).
-Not built, refused by name: TSVVolume and Imaris (.ims) sources.  ``timeout``, ``max_processors``, ``needed_memory`` and
+Not built, refused by name: Imaris (.ims) sources and any TSVVolume that is not ``ipp_amd.tsv.TSVVolume``.  ``timeout``, ``max_processors``, ``needed_memory`` and
 ``progress_bar_name`` are accepted and ignored.  Under ``torchrun`` every rank takes every WORLD_SIZE-th z group on its LOCAL_RANK
 device; rank 0 waits for the planes of the others and builds the npz.  Departures from the reference: INTEGRATION section 4e.
 """
@@ -158,6 +161,9 @@ def tif_save_path(destination, images, idx, rename=False, tif_prefix="img"):
 
 
 def _refuse_source(source):
+    from .tsv import TSVVolume
+    if isinstance(source, TSVVolume):
+        return
     if type(source).__name__ == "TSVVolume":
         raise NotImplementedError("source=TSVVolume: a TSVVolume source is not built (a folder of 2-D slices is)")
     if isinstance(source, (str, Path)) and Path(source).suffix.lower() == ".ims":
@@ -321,21 +327,38 @@ def parallel_image_processor(source, destination, fun=None, args=None, kwargs=No
     """parallel_image_processor.py:489 on the GPU, the reference's keywords and defaults.  Returns 0, or (0, down-sampled folder) with
     ``return_downsampled_path``."""
     import torch
+    from .tsv import TSVVolume, VExtent
     _refuse_source(source)
-    source, destination = Path(source), Path(destination)
-    if not source.is_dir():
-        raise RuntimeError("source can be either a tsv volume, an ims file path, or a 2D tiff series folder (the folder is built)")
+    is_tsv = isinstance(source, TSVVolume)
+    destination = Path(destination)
+    if not is_tsv:
+        source = Path(source)
+        if not source.is_dir():
+            raise RuntimeError("source can be either a tsv volume, an ims file path, or a 2D tiff series folder (the folder and the "
+                               "tsv volume are built)")
     destination.mkdir(exist_ok=True)
     downsampled_path = destination if downsampled_path is None else Path(downsampled_path)
     out_dtype = np.dtype(down_sampled_dtype)
     if out_dtype not in (np.float32, np.uint16, np.uint8):
         raise RuntimeError(f"requested downsampled format is not supported: down_sampled_dtype={down_sampled_dtype!r}")
 
-    images = natural_sorted([str(f) for f in source.iterdir() if f.is_file() and f.suffix.lower() in SUPPORTED_EXTENSIONS])
-    num_images = len(images)
-    assert num_images > 0, f"no .tif / .tiff / .raw / .png file in {source}"
+    if is_tsv:   # :578-590: the slices are the volume's planes, named {tif_prefix}_{idx:06}.tif (:194-199)
+        images, rename = None, True
+        whole = source.volume
+        num_images = whole.shape[0]
+        assert num_images > 0, "the TSVVolume holds no plane"
+    else:
+        images = natural_sorted([str(f) for f in source.iterdir() if f.is_file() and f.suffix.lower() in SUPPORTED_EXTENSIONS])
+        num_images = len(images)
+        assert num_images > 0, f"no .tif / .tiff / .raw / .png file in {source}"
+
+    def read_planes(first, last):
+        """planes [first, last] of the TSVVolume as one device stack (one merge launch)"""
+        return source.imread_device(VExtent(whole.x0, whole.x1, whole.y0, whole.y1, whole.z0 + first, whole.z0 + last + 1))
 
     def read_source(idx):
+        if is_tsv:
+            return read_planes(idx, idx)[0].cpu().numpy()
         img = pystripe.imread_tif_raw_png(Path(images[idx]))
         if img is None:
             raise RuntimeError(f"cannot read {images[idx]}")
@@ -343,8 +366,8 @@ def parallel_image_processor(source, destination, fun=None, args=None, kwargs=No
             img = img[:, :, channel]
         return img
 
-    first = read_source(0)
-    shape, rotated = tuple(first.shape), rotation in (90, 270)
+    shape = tuple(whole.shape[1:3]) if is_tsv else tuple(read_source(0).shape)
+    rotated = rotation in (90, 270)
     need_down_sampling = source_voxel is not None and target_voxel is not None
     steps, rounds, t3 = 1, 0, None
     if need_down_sampling:
@@ -362,8 +385,10 @@ def parallel_image_processor(source, destination, fun=None, args=None, kwargs=No
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     capi.require_gpu()
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)) % max(torch.cuda.device_count(), 1))
+    if is_tsv and source.device is not None and torch.device(source.device) != device:
+        raise ValueError(f"source.device={source.device!r}: the per-slice pass of this rank works on {device}")
     on_device = fun is pystripe.process_img
-    writes_images = save_images and (fun is not None or rotation in (90, 180, 270))
+    writes_images = save_images and (is_tsv or fun is not None or rotation in (90, 180, 270))   # :355
     plans = {}
 
     def plan_for(kind):
@@ -409,7 +434,14 @@ def parallel_image_processor(source, destination, fun=None, args=None, kwargs=No
                     slices[k] = None if img is None else to_device(img)
             else:
                 todo.append(k)
-        if todo and on_device:
+        if todo and on_device and is_tsv:   # the planes of the group from ONE merge; they stay on the device
+            with torch.cuda.device(device):
+                stack = read_planes(indices[todo[0]], indices[todo[-1]])
+            if len(todo) != todo[-1] - todo[0] + 1:   # resumed: some planes in between exist already
+                stack = _stack([stack[k - todo[0]] for k in todo])
+            for k, r in zip(todo, list(rotate(_call(fun, stack, args, kwargs)))):
+                slices[k] = r
+        elif todo and on_device:
             src = [read_source(indices[k]) for k in todo]
             if len({(s.shape, s.dtype) for s in src}) == 1:   # the whole group through every launch together
                 stack = torch.from_numpy(np.stack(src)).to(device)
@@ -488,7 +520,8 @@ def _parse_args(argv=None):
     import argparse
     p = argparse.ArgumentParser(prog="parallel_image_processor.py", allow_abbrev=False,
                                 description="isotropic down-sampling of a folder of 2-D slices on the GPU")
-    p.add_argument("--input", "-i", required=True, help="folder of 2-D .tif / .tiff / .raw / .png slices")
+    p.add_argument("--input", "-i", required=True, help="folder of 2-D .tif / .tiff / .raw / .png slices, or a TeraStitcher project "
+                   ".xml with displacements (merged on the device: ipp_amd.tsv.TSVVolume)")
     p.add_argument("--output", "-o", required=True, help="destination folder (rotated slices are written here)")
     p.add_argument("--voxel_size", type=float, nargs=3, required=True, metavar=("Z", "Y", "X"))
     p.add_argument("--voxel_size_target", type=float, required=True, metavar="T")
@@ -497,12 +530,21 @@ def _parse_args(argv=None):
     p.add_argument("--down_sampled_dtype", default="float32", choices=("float32", "uint16", "uint8"))
     p.add_argument("--no-alternating", dest="alternating", action="store_false", help="every halving round is mean / mean")
     p.add_argument("--rename", action="store_true", help="full-resolution outputs are named img_000000.tif, ...")
+    p.add_argument("--alt_stack_dir", default=None, help="project XML: stacks folder of another channel")
+    p.add_argument("--cosine_blending", action="store_true", help="project XML: the float16 cosine blend instead of the maximum")
+    p.add_argument("--ignore_z_offsets", action="store_true", help="project XML: the D displacements are dropped")
     return p.parse_args(argv)
 
 
 def main(argv=None):
     a = _parse_args(argv)
-    rc, folder = parallel_image_processor(a.input, a.output, source_voxel=tuple(a.voxel_size), target_voxel=a.voxel_size_target,
+    source = a.input
+    if str(a.input).lower().endswith(".xml"):
+        from .tsv import TSVVolume
+        source = TSVVolume(a.input, ignore_z_offsets=a.ignore_z_offsets, alt_stack_dir=a.alt_stack_dir, cosine_blending=a.cosine_blending)
+    elif a.alt_stack_dir is not None or a.cosine_blending or a.ignore_z_offsets:
+        raise SystemExit("--alt_stack_dir, --cosine_blending and --ignore_z_offsets go with a project .xml as --input")
+    rc, folder = parallel_image_processor(source, a.output, source_voxel=tuple(a.voxel_size), target_voxel=a.voxel_size_target,
                                           downsampled_path=a.downsampled_path, rotation=a.rotation, down_sampled_dtype=a.down_sampled_dtype,
                                           alternating_downsampling_method=a.alternating, rename=a.rename, return_downsampled_path=True)
     print(f"parallel_image_processor: down-sampled planes in {folder}")

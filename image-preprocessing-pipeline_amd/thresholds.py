@@ -267,11 +267,15 @@ class SliceParams(dict):
 
 
 class _Slices:
-    """A folder of 2-D slices (natural order, the library's TIFF reader) or a [nz, ny, nx] array / tensor, one slice at a time."""
+    """A folder of 2-D slices (natural order, the library's TIFF reader), a [nz, ny, nx] array / tensor or an ``ipp_amd.tsv.TSVVolume``
+    (process_images.py:610-615; its planes are merged on the device and stay there), one slice at a time."""
 
     def __init__(self, source):
-        self.files = self.stack = None
-        if isinstance(source, (str, os.PathLike)):
+        from .tsv import TSVVolume
+        self.files = self.stack = self.volume = None
+        if isinstance(source, TSVVolume):
+            self.volume = source
+        elif isinstance(source, (str, os.PathLike)):
             from .parallel_image_processor import natural_sorted
             from .pystripe import SUPPORTED_EXTENSIONS
             path = Path(source)
@@ -285,9 +289,15 @@ class _Slices:
             self.stack = source
 
     def __len__(self):
+        if self.volume is not None:
+            return int(self.volume.volume.shape[0])
         return len(self.files) if self.files is not None else int(self.stack.shape[0])
 
     def __getitem__(self, z):
+        if self.volume is not None:
+            from .tsv import VExtent
+            v = self.volume.volume
+            return self.volume.imread_device(VExtent(v.x0, v.x1, v.y0, v.y1, v.z0 + z, v.z0 + z + 1))[0]
         if self.stack is not None:
             return self.stack[z]
         from .pystripe import imread_tif_raw_png
@@ -336,7 +346,8 @@ def estimate_slice_params(source, need_bleach_correction=True, need_16bit_to_8bi
     75 % of the depth, the bit shift of each at the 99.99th percentile of the samples above ``clip_max``.  A uniform slice, or one
     multi-Otsu cannot split, moves that index up by one (past the last slice: ValueError).  Returns the largest bit shift, the
     clips of the LAST slice (the reference overwrites them in its loop) and ``dark = round(expm1(clip_min))`` as the keywords of
-    ``process_img``; ``.slices`` are the three indices used.  ``source``: a folder of u8 / u16 slices or a [nz, ny, nx] array / tensor."""
+    ``process_img``; ``.slices`` are the three indices used.  ``source``: a folder of u8 / u16 slices, a [nz, ny, nx] array / tensor, or an
+    ``ipp_amd.tsv.TSVVolume``."""
     params = SliceParams(bleach_correction_clip_min=None, bleach_correction_clip_med=None, bleach_correction_clip_max=None,
                          bit_shift_to_right=8, dark=0)
     if not (need_16bit_to_8bit_conversion or need_bleach_correction):
