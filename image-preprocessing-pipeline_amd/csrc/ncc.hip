@@ -1,26 +1,16 @@
-// MIP-NCC pairwise tile registration on the device (replaces TeraStitcher/src/crossmips:
-// libcrossmips.cpp:101-515 norm_cross_corr_mips and the CPU/CUDA branches of compute_funcs.cu).
-//
-// Device side
-//   k_mips        one streaming pass over both overlap views -> 6 MIPs (compute_3_MIPs, :502-521).
-//                 A lane owns one column j of a 16-row band and keeps the xy maxima in registers; the
-//                 xz row maxima are reduced per wave with DPP shuffles, xz/yz partials are merged with
-//                 integer atomicMax on the float bit pattern (all values >= 0 as the MIPs start at 0).
-//   k_tile_sums   32x32 tile sums with the reference's FLOAT running sum in row/column order
-//                 (seq_cpu_compute_partial_sums, :474-500) -- bit-identical, one lane per tile.
-//   k_mip_mean / k_sat_rows / k_sat_cols   fp64 summed-area tables of (f - c0), (f - c0)^2 and of the float tile sums:
-//                 every term of compute_NCC (:1163-1292) except the cross term sum f*t becomes O(1) per shift, with
-//                 the reference's means (float tile sums + border pixels) reproduced exactly.
-//   k_ncc_blk / k_ncc_finish   cross terms sum f*t in fp64 for groups of 8 blocks of 4 x 8 shifts from LDS-staged MIP rows, partial sums per
-//                 row chunk added in a fixed order; replaces gpu_NCC_map/gpu_NCC_miss (:730-935).  Serves full maps and the
-//                 "missing entries" of the neighbourhood refinement alike.
-// Host side (this file, plain C++): argmax, neighbourhood refinement, peak widths and the final
-// alignment rules, kept bit-identical in float/int arithmetic to compute_funcs.cu:160-342,1294-1609.
+// MIP-NCC pairwise tile registration on the device (replaces TeraStitcher/src/crossmips: libcrossmips.cpp:101-515
+// norm_cross_corr_mips and the CPU/CUDA branches of compute_funcs.cu): the C ABI and the orchestration of a batch.  A batch goes
+// through the batched lag-transform pipeline (ncc_lag.hip) group by group; what that hands back, and geometries it does not take,
+// continue on the per-pair path (ncc_pair.hip).  The units of the family: ncc_internal.h.
 #include <atomic>
+#include <exception>
 #include <map>
+#include <string>
+#include <thread>
 
-#include "ncc_core.h"
-#include "ncc_lag.h"
+#include "ncc_internal.h"
+
+using namespace mi;
 
 namespace mi {
 static std::atomic<long long> g_ncc_stats[3];
@@ -34,39 +24,12 @@ extern "C" void mi_ncc_stats(long long* out3, int reset) {
     }
 }
 
-namespace mi {
-// the cached pair slots of a device (-1: all) are destroyed; their buffers return to the pool (mi_release_cached_memory)
-void ncc_drop_cached_slots(int dev) {
-    std::vector<std::unique_ptr<PairSlot>> drop;
-    {
-        std::lock_guard<std::mutex> g(g_slot_mu);
-        for (size_t i = 0; i < g_slots.size();)
-            if (dev < 0 || g_slots[i]->dev == dev) { drop.push_back(std::move(g_slots[i])); g_slots.erase(g_slots.begin() + i); }
-            else ++i;
-    }
-    ncc_lag_drop_cached(dev);
-}
-}  // namespace mi
-
-namespace {
 // MI_NCC_DIRECT=1: every pair takes the per-pair path (shift-by-shift fp64 cross terms, host-driven refinement) -- the A/B
 // reference of the batched lag-transform pipeline and its fallback
-bool force_direct() {
+static bool force_direct() {
     const char* e = std::getenv("MI_NCC_DIRECT");
     return e && *e && *e != '0';
 }
-
-// the per-pair path of one pair (also the careful path of pairs the batched pipeline hands back)
-int pair_direct(hipStream_t s, const float* A, const float* B, int dimk, int dimi, int dimj, int ni, int nj, int delayk, int delayi, int delayj,
-                int side, mi_ncc_params* p, mi_ncc_descr* out) {
-    PairPlan pl;
-    MI_TRY(plan_pair(dimk, dimi, dimj, 0, ni, nj, delayk, delayi, delayj, side, p, pl));
-    Workspace ws;
-    MI_TRY(pair_enqueue(s, A, B, dimi, dimj, pl, ws));
-    ncc_count(1, 1);
-    return pair_finish(s, ni, nj, side, p, pl, ws, out);
-}
-}  // namespace
 
 extern "C" void mi_ncc_default_params(int displ_max_V, int displ_max_H, int displ_max_D, mi_ncc_params* p) {
     if (!p) return;
@@ -279,8 +242,6 @@ static int ncc_batch_end(mi_ncc_batch_job& J, mi_ncc_params* params, mi_ncc_desc
     const int* nj = J.nj.data();
     const int* side = J.side.data();
     mi_ncc_params* wparams = J.params.data();
-    auto tile_a = [&](int q) { return J.ta[q]; };
-    auto tile_b = [&](int q) { return J.tb[q]; };
     const int n_todo = (int)todo.size();
     if (n_todo == 0) {
         if (params)
@@ -303,34 +264,34 @@ static int ncc_batch_end(mi_ncc_batch_job& J, mi_ncc_params* params, mi_ncc_desc
     std::vector<std::string> msgs(NT);
     auto worker = [&](int t) {
         // workspaces (device tables, pinned staging) and streams are kept between calls: setting them up costs milliseconds
-        struct Slot { std::unique_ptr<PairSlot> r; Workspace& ws; PairPlan pl; hipStream_t s; };
+        struct Slot { PairSlot& r; PairPlan pl; };
         int rc = use_device(dev);
-        std::unique_ptr<PairSlot> res[2] = {take_pair_slot(dev), take_pair_slot(dev)};
+        PairSlotPtr res[2] = {take_pair_slot(dev), take_pair_slot(dev)};  // (on any way out but the regular one they are destroyed)
         for (auto& r : res)
-            if (rc == MI_OK && (!r || !r->s || hipStreamWaitEvent(r->s, ev, 0) != hipSuccess))
+            if (rc == MI_OK && (!r || hipStreamWaitEvent(pair_slot_stream(*r), ev, 0) != hipSuccess))
                 rc = fail(MI_ERR_HIP, "mi_ncc_mips_batch: stream setup failed");
         if (rc != MI_OK) { msgs[t] = mi_last_error(); rcs[t] = rc; return; }
-        Slot slot[2] = {{nullptr, res[0]->ws, PairPlan(), res[0]->s}, {nullptr, res[1]->ws, PairPlan(), res[1]->s}};
+        Slot slot[2] = {{*res[0], PairPlan()}, {*res[1], PairPlan()}};
         int k = 0;  // index of the pair within this thread's sequence t, t + NT, ...
         for (int qi = t; rc == MI_OK; qi += NT, ++k) {
             if (qi < n_todo) {
                 const int q = todo[qi];
                 Slot& sl = slot[k & 1];
                 rc = plan_pair(dimk, dimi, dimj, 0, ni[q], nj[q], delayk, delayi, delayj, side[q], &wparams[q], sl.pl);
-                if (rc == MI_OK) rc = pair_enqueue(sl.s, tile_a(q), tile_b(q), dimi, dimj, sl.pl, sl.ws, fmt);
+                if (rc == MI_OK) rc = pair_enqueue(sl.r, J.ta[q], J.tb[q], dimi, dimj, sl.pl, fmt);
             }
             const int fi = qi - NT;
             if (fi >= 0 && fi < n_todo && rc == MI_OK) {
                 const int f = todo[fi];
                 Slot& pr = slot[(k - 1) & 1];
-                rc = pair_finish(pr.s, ni[f], nj[f], side[f], &wparams[f], pr.pl, pr.ws, &out[f]);
+                rc = pair_finish(pr.r, ni[f], nj[f], side[f], &wparams[f], pr.pl, &out[f]);
                 ncc_count(1, 1);
             }
             if (qi >= n_todo) break;
         }
         if (rc != MI_OK) msgs[t] = mi_last_error();
         for (auto& r : res) {
-            (void)hipStreamSynchronize(r->s);
+            (void)hipStreamSynchronize(pair_slot_stream(*r));
             give_pair_slot(std::move(r));
         }
         rcs[t] = rc;
@@ -455,7 +416,7 @@ extern "C" int mi_ncc_time_mips(int dev, void* stream, int n_pairs, const float*
     MI_REQUIRE(n_pairs > 0 && tiles && a_idx && b_idx, "mi_ncc_time_mips: null pointer");
     std::vector<const float*> pa(n_pairs), pb(n_pairs);
     for (int q = 0; q < n_pairs; ++q) { pa[q] = tiles[a_idx[q]]; pb[q] = tiles[b_idx[q]]; }
-    return ncc_time_mips(dev, as_stream(stream), n_pairs, pa.data(), pb.data(), dimk, dimi, dimj, ni, nj, side, reps, ms_per_launch);
+    return ncc_time_mips(as_stream(stream), n_pairs, pa.data(), pb.data(), dimk, dimi, dimj, ni, nj, side, reps, ms_per_launch);
 }
 
 static int time_mips_int(int bytes, int dev, void* stream, int n_pairs, const void* const* tiles, float scale, const int* a_idx, const int* b_idx,
@@ -470,7 +431,7 @@ static int time_mips_int(int bytes, int dev, void* stream, int n_pairs, const vo
     TileFmt fmt;
     fmt.bytes = bytes;
     fmt.scale = scale;
-    return ncc_time_mips(dev, as_stream(stream), n_pairs, pa.data(), pb.data(), dimk, dimi, dimj, ni, nj, side, reps, ms_per_launch, fmt);
+    return ncc_time_mips(as_stream(stream), n_pairs, pa.data(), pb.data(), dimk, dimi, dimj, ni, nj, side, reps, ms_per_launch, fmt);
 }
 extern "C" int mi_ncc_time_mips_u16(int dev, void* stream, int n_pairs, const unsigned short* const* tiles, float scale, const int* a_idx,
                                     const int* b_idx, int dimk, int dimi, int dimj, int ni, int nj, int side, int reps, float* ms_per_launch) {
@@ -496,15 +457,5 @@ extern "C" int mi_ncc_compute_map(int dev, void* stream, const float* mip1, cons
     MI_TRY(use_device(dev));
     MI_REQUIRE(mip1 && mip2 && map, "compute_NCC_map: null pointer");
     MI_REQUIRE(dimu > 0 && dimv > 0 && delayu >= 0 && delayv >= 0, "compute_NCC_map: invalid extents");
-    hipStream_t s = as_stream(stream);
-    const int nt = (dimu / TILE) * (dimv / TILE);
-    DevBuf ps, sat;
-    MI_TRY(ps.alloc(sizeof(float) * 2 * (size_t)(nt > 0 ? nt : 1)));
-    MI_TRY(sat.alloc(sizeof(double) * SatLayout(dimu, dimv).total));
-    SatView v1, v2;
-    MI_TRY(prepare_plane(s, mip1, mip2, dimu, dimv, ps.as<float>(), ps.as<float>() + (nt > 0 ? nt : 0), sat.as<double>(), &v1, &v2));
-    DevBuf partial;
-    MI_TRY(ncc_launch(s, mip1, mip2, dimu, dimv, delayu, delayv, v1, v2, nullptr, 0, nullptr, 0, partial, map));
-    MI_HIP(hipStreamSynchronize(s));  // ps / sat / partial die at scope exit
-    return MI_OK;
+    return pair_map(as_stream(stream), mip1, mip2, dimu, dimv, delayu, delayv, map);
 }

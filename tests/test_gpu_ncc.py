@@ -144,7 +144,7 @@ def test_wide_search_and_wide_mips_vs_oracle(dev):
 
 
 def test_overlap_wider_than_the_prefetch_registers_vs_oracle(dev):
-    """An xy plane whose SHORT axis is 1650 samples: a tile of the correlation kernel (ncc_lag.hip:k_lag_mac) no longer fits the registers
+    """An xy plane whose SHORT axis is 1650 samples: a tile of the correlation kernel (ncc_lag_fft.hip:k_lag_mac) no longer fits the registers
     that carry the next tile's spectra, so the kernel variant that fetches the next tile behind the current one runs (and one
     frequency per work-group instead of four)."""
     from ipp_amd import crossmips
@@ -434,3 +434,55 @@ def test_mips_shape_sweep_is_exact(dev):
             assert np.array_equal(got[k], v.max(axis=0)), (dimk, dimi, dimj, side, "xy")
             assert np.array_equal(got[k + 1], v.max(axis=2).T), (dimk, dimi, dimj, side, "xz")
             assert np.array_equal(got[k + 2], v.max(axis=1).T), (dimk, dimi, dimj, side, "yz")
+
+
+def test_timed_mips_launch_goes_through_the_launcher(dev):
+    """mi_ncc_time_mips / _u16 / _u8 (the bench's roofline hook) launch the MIP pass through the launcher every other caller uses, with
+    the zeroing launch and the deep-stack reductions switched off: two pairs per call, both sides, two repetitions, for the float pass
+    of shallow stacks (6 slices: k_mips5), of deep ones (33 slices: k_mips) and the integer passes (4 slices).  Each call returns MI_OK
+    and a finite, positive duration; bad arguments are refused; compute_3_MIPs on the same tiles (the integer ones converted like the
+    reference converts them) is exact right afterwards.  Run alone on an MI355X, first use of the kernels included: 0.39 s."""
+    import ctypes as C
+    from ipp_amd import capi, crossmips
+    lib, rng = capi.lib(), np.random.default_rng(7)
+    stream = capi.current_stream_ptr(dev)
+    a_idx, b_idx = (C.c_int * 2)(0, 1), (C.c_int * 2)(1, 2)
+    sides = ((0, 9, 0), (1, 0, 13))   # (side, ni, nj): north-south from row 9, west-east from column 13 (first column block partial)
+
+    def timed(fn, tiles, shape, extra, side, ni, nj, reps=2, dimj=None):
+        ptrs = (C.c_void_p * 3)(*[t.data_ptr() for t in tiles])
+        ms = C.c_float(float("nan"))
+        rc = fn(dev.index, stream, 2, ptrs, *extra, a_idx, b_idx, shape[0], shape[1], dimj or shape[2], ni, nj, side, reps, C.byref(ms))
+        return rc, ms.value
+
+    floats = {}
+    for shape in ((6, 40, 72), (33, 40, 72)):
+        host = [rng.random(shape, dtype=np.float32) for _ in range(3)]
+        floats[shape] = (host, [torch.from_numpy(h).to(dev) for h in host])
+        for side, ni, nj in sides:
+            rc, ms = timed(lib.mi_ncc_time_mips, floats[shape][1], shape, (), side, ni, nj)
+            assert rc == capi.MI_OK and np.isfinite(ms) and ms > 0, (shape, side, rc, ms)
+    shape = (4, 40, 72)
+    ints = {}
+    for fn, dtype, tdtype, scale in ((lib.mi_ncc_time_mips_u16, np.uint16, np.int16, 65535.0), (lib.mi_ncc_time_mips_u8, np.uint8, np.uint8, 255.0)):
+        host = [rng.integers(0, np.iinfo(dtype).max, shape, dtype=dtype, endpoint=True) for _ in range(3)]
+        ints[dtype] = [torch.from_numpy(h.view(tdtype)).to(dev) for h in host]   # (the bytes are what counts)
+        for side, ni, nj in sides:
+            rc, ms = timed(fn, ints[dtype], shape, (C.c_float(scale),), side, ni, nj)
+            assert rc == capi.MI_OK and np.isfinite(ms) and ms > 0, (dtype, side, rc, ms)
+        # compute_mips is the float entry: it gets the integer tiles as they lie on the device after the timed launches, converted like
+        # the reference converts them (sample / scale in float32, tiff2D.cpp:606-610)
+        top = torch.tensor(scale, dtype=torch.float32, device=dev)   # (a tensor: by a Python scalar torch multiplies with the reciprocal)
+        wide = [torch.div((t.to(torch.int32) & int(scale)).to(torch.float32), top) for t in ints[dtype]]
+        floats[shape + (dtype,)] = ([h.astype(np.float32) / np.float32(scale) for h in host], wide)
+    assert timed(lib.mi_ncc_time_mips, floats[(6, 40, 72)][1], (6, 40, 72), (), 0, 9, 0, reps=0)[0] == capi.MI_ERR_INVALID
+    assert timed(lib.mi_ncc_time_mips_u8, ints[np.uint8], shape, (C.c_float(255.0),), 1, 0, 12, dimj=70)[0] == capi.MI_ERR_INVALID
+    for fshape, (host, tiles) in floats.items():
+        for side, ni, nj in sides:
+            for a, b in ((0, 1), (1, 2)):
+                got = [m.cpu().numpy() for m in crossmips.compute_mips(tiles[a], tiles[b], ni, nj, side)]
+                va, vb = host[a][:, ni:, nj:], host[b][:, :fshape[1] - ni, :fshape[2] - nj]
+                for k, v in ((0, va), (3, vb)):
+                    assert np.array_equal(got[k], v.max(axis=0)), (fshape, side, "xy")
+                    assert np.array_equal(got[k + 1], v.max(axis=2).T), (fshape, side, "xz")
+                    assert np.array_equal(got[k + 2], v.max(axis=1).T), (fshape, side, "yz")
