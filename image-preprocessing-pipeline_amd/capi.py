@@ -70,6 +70,7 @@ class PystripeParams(C.Structure):
 
 
 PS_MAX_LEVELS = 24  # MI_PS_MAX_LEVELS
+PS_MAX_TAPS = 128  # MI_PS_MAX_TAPS
 PS_BLEACH_LDS_ROW = 20436  # MI_PS_BLEACH_LDS_ROW
 
 
@@ -235,6 +236,8 @@ SIGNATURES = {
     "mi_tiff_lzw_encode": (_i, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64)]),
     # mi_pystripe.h
     "mi_pystripe_plan_create": (_i, [_i, _i, _i, _i, C.POINTER(PystripeParams), C.POINTER(_vp)]),
+    "mi_pystripe_plan_create_wavelet": (_i, [_i, _i, _i, _i, C.POINTER(PystripeParams), C.POINTER(C.c_double), _i, C.POINTER(_vp)]),
+    "mi_pystripe_derive_wavelet": (_i, [_i, _i, _i, C.POINTER(PystripeParams), _i, C.POINTER(PystripeInfo)]),
     "mi_pystripe_plan_destroy": (_i, [_vp]),
     "mi_pystripe_plan_info": (_i, [_vp, C.POINTER(PystripeInfo)]),
     "mi_pystripe_derive": (_i, [_i, _i, _i, C.POINTER(PystripeParams), C.POINTER(PystripeInfo)]),

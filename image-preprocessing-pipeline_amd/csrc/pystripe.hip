@@ -21,6 +21,8 @@
 //             L is log1p on load and never stored); a work-group per row runs sosfiltfilt's forward-backward first-order
 //             recurrence in float64 as a scan of affine maps over the clipped, odd-extended row in LDS and writes F and its row
 //             maximum; a block per tile reduces the maxima; the apply pass hands (L / F) * max F to the same store.
+//   wavelets  the kernels named above are db9's (mi_pystripe_plan_create); mi_pystripe_plan_create_wavelet runs their counterparts
+//             for any even tap count up to MI_PS_MAX_TAPS (the *_gen_kernel section): same load, notch, store and bleach route.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -434,9 +436,217 @@ __global__ void __launch_bounds__(256) syn_rows_kernel(const float* lo1, const f
     }
 }
 
+// ---- any orthogonal wavelet of L taps (L even, 2 .. MI_PS_MAX_TAPS) ---------------------------------------------------------------
+// The transform above with the tap count as a run-time value: m = (n + L - 1) / 2 coefficients, 2 m - L + 2 samples back.  4 x 90
+// coefficients do not fit a wave's scalar registers, so the four filters lie in device memory, each with kTabPad zeros on either
+// side, and are read at wave-uniform addresses inside loops that are not unrolled by L; the zeros let a thread that makes four
+// neighbouring outputs run one loop over all the inputs they share.  The column passes stage their input rows in LDS, so a row is
+// read once per block instead of L / 2 times.
+
+constexpr int kTabPad = 8;      // zeros on either side of a filter in the table
+constexpr int kColRows = 16;    // output rows of a block of the column analysis
+constexpr int kColPairs = 16;   // output row pairs of a block of the column synthesis
+
+__device__ __forceinline__ int wave_index() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+
+// analysis along axis -1: 2 * 256 + L - 2 inputs of a block in LDS (the symmetric extension may reflect more than once: L - 2 can
+// exceed the row); a thread takes its taps two at a time as one 8-byte LDS read.
+__global__ void __launch_bounds__(kRowBlock) ana_rows_gen_kernel(Src s, int n, int m, float* __restrict__ Lo, float* __restrict__ Hi,
+                                                                 i64 out_tile_stride, const float* __restrict__ tab, int L) {
+    __shared__ __attribute__((aligned(16))) float sh[2 * kRowBlock + MI_PS_MAX_TAPS - 2];
+    const int i0 = blockIdx.x * kRowBlock, row = blockIdx.y;
+    const i64 tile = blockIdx.z;
+    const int base = 2 * i0 - (L - 2);
+    const int cnt = 2 * min(kRowBlock, m - i0) + L - 2;
+    for (int q = threadIdx.x; q < cnt; q += kRowBlock) sh[q] = src_load(s, tile, row, pad_index(sym_index(base + q, n), s.pad, s.nx, s.mode));
+    __syncthreads();
+    const int i = i0 + threadIdx.x;
+    if (i >= m) return;
+    const float* lo_d = tab + kTabPad;
+    const float* hi_d = tab + (L + 2 * kTabPad) + kTabPad;
+    const float2* v2 = reinterpret_cast<const float2*>(sh) + threadIdx.x;   // sh[2 tid + 2 c]: tap L - 1 - 2 c, then tap L - 2 - 2 c
+    float lo = 0.f, hi = 0.f;
+    for (int c = 0; c < L / 2; ++c) {
+        const float2 v = v2[c];
+        const int t = L - 2 - 2 * c;
+        lo = fmaf(lo_d[t + 1], v.x, lo);
+        hi = fmaf(hi_d[t + 1], v.x, hi);
+        lo = fmaf(lo_d[t], v.y, lo);
+        hi = fmaf(hi_d[t], v.y, hi);
+    }
+    const i64 o = tile * out_tile_stride + (i64)row * m + i;
+    Lo[o] = lo;
+    Hi[o] = hi;
+}
+
+// analysis along axis -2: a block makes kColRows output rows of 64 columns from the (2 kColRows + L - 2) x 64 segments of L and H in
+// LDS (rows through the padding map at the first level; all of them are staged, also behind the last output row: a zero filter
+// entry must not meet an unwritten word).  A wave makes four neighbouring output rows: staged row 2 il0 + q meets tap L - 1 - q + 2 j
+// of output il0 + j.
+__global__ void __launch_bounds__(256) ana_cols_gen_kernel(const float* __restrict__ Lo, const float* __restrict__ Hi, i64 in_tile_stride, int n,
+                                                           int m, int w, int pad, int src_rows, int mode, float* __restrict__ A,
+                                                           i64 a_tile_stride, float* __restrict__ cH, float* __restrict__ cV,
+                                                           float* __restrict__ cD, i64 d_tile_stride, const float* __restrict__ tab, int L) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int nrows = 2 * kColRows + L - 2;
+    float* shL = reinterpret_cast<float*>(smem);
+    float* shH = shL + nrows * 64;
+    const int lane = threadIdx.x & 63, wave = wave_index();
+    const int x = blockIdx.x * 64 + lane, i0 = blockIdx.y * kColRows;
+    const i64 tile = blockIdx.z;
+    const int base = 2 * i0 - (L - 2);
+    const float* l = Lo + tile * in_tile_stride + x;
+    const float* h = Hi + tile * in_tile_stride + x;
+    for (int q = wave; q < nrows; q += 4) {
+        const int r = pad_index(sym_index(base + q, n), pad, src_rows, mode);
+        float lv = 0.f, hv = 0.f;
+        if (x < w) {
+            lv = l[(i64)r * w];
+            hv = h[(i64)r * w];
+        }
+        shL[q * 64 + lane] = lv;
+        shH[q * 64 + lane] = hv;
+    }
+    __syncthreads();
+    const int il0 = 4 * wave;
+    if (i0 + il0 >= m) return;
+    const float* lo_d = tab + kTabPad;
+    const float* hi_d = tab + (L + 2 * kTabPad) + kTabPad;
+    const float* pl = shL + 2 * il0 * 64 + lane;
+    const float* ph = shH + 2 * il0 * 64 + lane;
+    float a[4] = {0.f, 0.f, 0.f, 0.f}, ch[4] = {0.f, 0.f, 0.f, 0.f}, cv[4] = {0.f, 0.f, 0.f, 0.f}, cd[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < L + 6; q += 2) {
+        const float l0 = pl[q * 64], h0 = ph[q * 64], l1 = pl[(q + 1) * 64], h1 = ph[(q + 1) * 64];
+        const int t0 = L - 1 - q;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float fl0 = lo_d[t0 + 2 * j], fh0 = hi_d[t0 + 2 * j], fl1 = lo_d[t0 - 1 + 2 * j], fh1 = hi_d[t0 - 1 + 2 * j];
+            a[j] = fmaf(fl0, l0, a[j]);
+            ch[j] = fmaf(fh0, l0, ch[j]);
+            cv[j] = fmaf(fl0, h0, cv[j]);
+            cd[j] = fmaf(fh0, h0, cd[j]);
+            a[j] = fmaf(fl1, l1, a[j]);
+            ch[j] = fmaf(fh1, l1, ch[j]);
+            cv[j] = fmaf(fl1, h1, cv[j]);
+            cd[j] = fmaf(fh1, h1, cd[j]);
+        }
+    }
+    if (x >= w) return;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = i0 + il0 + j;
+        if (i >= m) break;
+        const i64 o = (i64)i * w + x;
+        A[tile * a_tile_stride + o] = a[j];
+        cH[tile * d_tile_stride + o] = ch[j];
+        cV[tile * d_tile_stride + o] = cv[j];
+        cD[tile * d_tile_stride + o] = cd[j];
+    }
+}
+
+// synthesis along axis -2: a block makes kColPairs row pairs (2 p, 2 p + 1) of 64 columns from rows p .. p + L / 2 - 1 of its two
+// inputs, staged in LDS (zeros behind the last coefficient row m - 1).  blockIdx.z = 2 * tile + which, as in syn_cols_kernel.  A wave
+// makes four neighbouring pairs: staged row pl0 + q meets taps L - 2 - 2 (q - j) (even output) and L - 1 - 2 (q - j) (odd) of pair pl0 + j.
+__global__ void __launch_bounds__(256) syn_cols_gen_kernel(const float* __restrict__ a, i64 a_tile_stride, int a_stride, const float* __restrict__ cH,
+                                                           const float* __restrict__ cV, const float* __restrict__ cD, i64 d_tile_stride, int w,
+                                                           int m, int p0, int p1, int s0, float* __restrict__ lo1, float* __restrict__ hi1,
+                                                           i64 out_tile_stride, const float* __restrict__ tab, int L) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int half = L / 2, nrows = kColPairs + half - 1;
+    float* shA = reinterpret_cast<float*>(smem);
+    float* shD = shA + nrows * 64;
+    const int lane = threadIdx.x & 63, wave = wave_index();
+    const int x = blockIdx.x * 64 + lane, pb = p0 + blockIdx.y * kColPairs;
+    const i64 tile = blockIdx.z >> 1;
+    const int which = blockIdx.z & 1;
+    const float* lo = (which ? cV + tile * d_tile_stride : a + tile * a_tile_stride) + x;
+    const float* hi = (which ? cD : cH) + tile * d_tile_stride + x;
+    const int lo_stride = which ? w : a_stride;
+    for (int q = wave; q < nrows; q += 4) {
+        const int r = pb + q;
+        float av = 0.f, dv = 0.f;
+        if (x < w && r < m) {
+            av = lo[(i64)r * lo_stride];
+            dv = hi[(i64)r * w];
+        }
+        shA[q * 64 + lane] = av;
+        shD[q * 64 + lane] = dv;
+    }
+    __syncthreads();
+    const int pl0 = 4 * wave;
+    if (pb + pl0 >= p1) return;
+    const int TS = L + 2 * kTabPad;
+    const float* lo_r = tab + 2 * TS + kTabPad;
+    const float* hi_r = tab + 3 * TS + kTabPad;
+    const float* pa = shA + pl0 * 64 + lane;
+    const float* pd = shD + pl0 * 64 + lane;
+    float e[4] = {0.f, 0.f, 0.f, 0.f}, o[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < half + 3; ++q) {
+        const float av = pa[q * 64], dv = pd[q * 64];
+        const int t0 = L - 2 - 2 * q;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            e[j] = fmaf(av, lo_r[t0 + 2 * j], e[j]);
+            e[j] = fmaf(dv, hi_r[t0 + 2 * j], e[j]);
+            o[j] = fmaf(av, lo_r[t0 + 2 * j + 1], o[j]);
+            o[j] = fmaf(dv, hi_r[t0 + 2 * j + 1], o[j]);
+        }
+    }
+    if (x >= w) return;
+    float* dst = (which ? hi1 : lo1) + tile * out_tile_stride + x;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int p = pb + pl0 + j;
+        if (p >= p1) break;
+        dst[(i64)(2 * p) * w] = e[j];
+        if (2 * p + 1 < s0) dst[(i64)(2 * p + 1) * w] = o[j];
+    }
+}
+
+// synthesis along axis -1: the 256 + L / 2 - 1 inputs of a block's 256 pairs in LDS.  FINAL as in syn_rows_kernel.
+template <bool FINAL>
+__global__ void __launch_bounds__(256) syn_rows_gen_kernel(const float* __restrict__ lo1, const float* __restrict__ hi1, i64 in_tile_stride, int w,
+                                                           int y0, int p0, int p1, int s1, float* __restrict__ out, i64 out_tile_stride, Sink k,
+                                                           const float* __restrict__ tab, int L) {
+    __shared__ float shA[256 + MI_PS_MAX_TAPS / 2 - 1], shD[256 + MI_PS_MAX_TAPS / 2 - 1];
+    const int pb = p0 + blockIdx.x * 256, y = y0 + blockIdx.y;
+    const i64 tile = blockIdx.z;
+    const int half = L / 2, cnt = min(256, p1 - pb) + half - 1;
+    const float* lo = lo1 + tile * in_tile_stride + (i64)y * w + pb;
+    const float* hi = hi1 + tile * in_tile_stride + (i64)y * w + pb;
+    for (int q = threadIdx.x; q < cnt; q += 256) {
+        shA[q] = lo[q];
+        shD[q] = hi[q];
+    }
+    __syncthreads();
+    const int p = pb + threadIdx.x;
+    if (p >= p1) return;
+    const int TS = L + 2 * kTabPad;
+    const float* lo_r = tab + 2 * TS + kTabPad;
+    const float* hi_r = tab + 3 * TS + kTabPad;
+    float e = 0.f, o = 0.f;
+    for (int d = 0; d < half; ++d) {
+        const float av = shA[threadIdx.x + d], dv = shD[threadIdx.x + d];
+        const int t = L - 2 - 2 * d;
+        e = fmaf(av, lo_r[t], e);
+        e = fmaf(dv, hi_r[t], e);
+        o = fmaf(av, lo_r[t + 1], o);
+        o = fmaf(dv, hi_r[t + 1], o);
+    }
+    if (FINAL) {
+        const int yy = y - k.pad, x0 = 2 * p - k.pad;
+        if (x0 >= 0 && x0 < k.nx) sink_store(k, tile, yy, x0, e);
+        if (x0 + 1 >= 0 && x0 + 1 < k.nx) sink_store(k, tile, yy, x0 + 1, o);
+    } else {
+        float* dst = out + tile * out_tile_stride + (i64)y * s1;
+        dst[2 * p] = e;
+        if (2 * p + 1 < s1) dst[2 * p + 1] = o;
+    }
+}
+
 // ---- bleach correction (correct_bleaching :501, butter_lowpass_filter :492) -----------------------------------------------------
 
-constexpr int kBleachExt = 6;                          // sosfiltfilt's padlen for one section
+constexpr int kBleachExt = 6;                         // sosfiltfilt's padlen for one section
 constexpr int kBleachMaxThreads = 1024;
 constexpr size_t kBleachLds = 160 * 1024;              // all of a CU's LDS
 constexpr size_t kBleachTotals = (kBleachMaxThreads / 64) * sizeof(double2);   // the scan's wave totals, behind the row
@@ -650,7 +860,7 @@ int pad_size(int ny, int nx, double sigma) {   // calculate_pad_size :681
     return notch_rise_point(sigma, std::min(r, 0.5));
 }
 
-int max_level(int n) { return n >= LF - 1 ? std::max((int)std::floor(std::log2((double)n / (LF - 1))), 0) : 0; }   // pywt.dwt_max_level
+int max_level(int n, int L) { return n >= L - 1 ? std::max((int)std::floor(std::log2((double)n / (L - 1))), 0) : 0; }   // pywt.dwt_max_level
 
 size_t round16(size_t v) { return (v + 15) / 16 * 16; }
 
@@ -668,6 +878,9 @@ struct Plan {
     int passes = 0;
     Bleach bq{};
     Filters f{};
+    int L = LF;               // taps; generic: the run-time-length kernels with their filter table (mi_pystripe_plan_create_wavelet)
+    bool generic = false;
+    DevBuf tab_buf;
     int h[MI_PS_MAX_LEVELS + 1] = {0}, w[MI_PS_MAX_LEVELS + 1] = {0};   // extents per level, [0] = padded image
     // per-tile scratch, offsets in floats
     size_t off_stage = 0, off_P = 0, off_rowL = 0, off_rowH = 0, off_A[MI_PS_MAX_LEVELS + 1] = {0}, off_cH[MI_PS_MAX_LEVELS + 1] = {0},
@@ -750,22 +963,31 @@ int derive(int ny_in, int nx_in, int in_dtype, const mi_pystripe_params& q, Plan
         I.padded_nx = I.nx + 2 * I.base_pad + I.pad_x;
         MI_REQUIRE((i64)I.padded_ny * I.padded_nx < (1ll << 31), "mi_pystripe: padded tile of %d x %d samples", I.padded_ny, I.padded_nx);
         MI_REQUIRE(I.padded_ny <= 65535, "mi_pystripe: padded tile of %d rows (at most 65535)", I.padded_ny);
-        I.levels = q.level > 0 ? q.level : std::min(max_level(I.padded_ny), max_level(I.padded_nx));
-        MI_REQUIRE(I.levels >= 1, "mi_pystripe: no wavelet level for a padded tile of %d x %d", I.padded_ny, I.padded_nx);
+        // the automatic level is 0 where a padded extent is below L - 1 (never for db9: 34 samples at least): wavedec2 then returns the
+        // approximation alone and the filter leaves the log image as it is
+        const int L = P.L;
+        I.levels = q.level > 0 ? q.level : std::min(max_level(I.padded_ny, L), max_level(I.padded_nx, L));
         P.h[0] = I.padded_ny; P.w[0] = I.padded_nx;
         for (int l = 1; l <= I.levels; ++l) {
-            P.h[l] = (P.h[l - 1] + LF - 1) / 2;
-            P.w[l] = (P.w[l - 1] + LF - 1) / 2;
+            P.h[l] = (P.h[l - 1] + L - 1) / 2;
+            P.w[l] = (P.w[l - 1] + L - 1) / 2;
             I.coef_ny[l - 1] = P.h[l]; I.coef_nx[l - 1] = P.w[l];
-            // a synthesis pair reads rows p .. p + 8 of a level: s = 2 m - 16 outputs need m >= 9, true for every m >= (0 + 17) / 2 + 1
-            MI_REQUIRE(P.h[l] >= 9 && P.w[l] >= 9, "mi_pystripe: level %d has %d x %d coefficients", l, P.h[l], P.w[l]);
+            // a synthesis pair reads rows p .. p + L / 2 - 1 of a level: s = 2 m - L + 2 outputs need m >= L / 2, true for every
+            // m = (n + L - 1) / 2 with n >= 1
+            MI_REQUIRE(P.h[l] >= L / 2 && P.w[l] >= L / 2, "mi_pystripe: level %d has %d x %d coefficients", l, P.h[l], P.w[l]);
         }
-        if (P.passes == 2) { P.sz_P = (size_t)P.h[0] * P.w[0]; P.off_P = take(P.sz_P); }
-        P.sz_row = (size_t)(P.h[0] + 1) * P.w[1];   // L / H of the first level; lo1 / hi1 of the synthesis (one more row when odd)
-        P.off_rowL = take(P.sz_row);
-        P.off_rowH = take(P.sz_row);
+        if (P.passes == 2 && I.levels) { P.sz_P = (size_t)P.h[0] * P.w[0]; P.off_P = take(P.sz_P); }
+        // L / H of a level's analysis (h[l - 1] rows of w[l]); lo1 / hi1 of its synthesis (2 h[l] - L + 2 <= h[l - 1] + 1 rows).  The
+        // first level is the largest while the extents are L - 1 or more; an explicit level on a shorter extent n GROWS it towards
+        // L - 1 ((n + L - 1) / 2 > n), so the largest level is looked for.
+        for (int l = 1; l <= I.levels; ++l) P.sz_row = std::max(P.sz_row, (size_t)(P.h[l - 1] + 1) * P.w[l]);
+        if (I.levels) {
+            P.off_rowL = take(P.sz_row);
+            P.off_rowH = take(P.sz_row);
+        }
         for (int l = 1; l <= I.levels; ++l) {
-            P.sz_A[l] = (size_t)(P.h[l] + 1) * (P.w[l] + 1);   // also holds the level's reconstruction (2 m' - 16 <= m + 1)
+            // also holds the reconstruction of level l + 1: with m' = (m + L - 1) / 2, 2 m' - L + 2 <= m + 1 for every L
+            P.sz_A[l] = (size_t)(P.h[l] + 1) * (P.w[l] + 1);
             P.sz_d[l] = (size_t)P.h[l] * P.w[l];
             P.off_A[l] = take(P.sz_A[l]);
             P.off_cH[l] = take(P.sz_d[l]);
@@ -919,6 +1141,34 @@ int run_bleach(Plan& P, hipStream_t st, const Src& L, const Sink& k, int cnt) {
     return launch_check("bleach_apply_kernel");
 }
 
+// the dynamic-LDS limit of a kernel, raised to one launch's need (see launch_notch)
+int raise_lds(const void* kernel, size_t lds) {
+    if (lds > 48 * 1024) MI_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return MI_OK;
+}
+
+// The four filters of the orthogonal wavelet with the reconstruction low-pass rec_lo[L] as float32, by the rule of make_filters(),
+// each between kTabPad zeros: [lo_d | hi_d | lo_r | hi_r], L + 2 kTabPad floats each.
+int upload_filter_table(Plan& P, const double* rec_lo) {
+    const int L = P.L, TS = L + 2 * kTabPad;
+    std::vector<float> t(4 * (size_t)TS, 0.f);
+    for (int i = 0; i < L; ++i) {
+        const float lo_r = (float)rec_lo[i], hi_r = (float)(rec_lo[L - 1 - i] * ((i & 1) ? -1.0 : 1.0));   // qmf
+        t[2 * TS + kTabPad + i] = lo_r;
+        t[3 * TS + kTabPad + i] = hi_r;
+        t[0 * TS + kTabPad + (L - 1 - i)] = lo_r;
+        t[1 * TS + kTabPad + (L - 1 - i)] = hi_r;
+    }
+    MI_TRY(P.tab_buf.alloc(t.size() * sizeof(float)));
+    MI_HIP(hipMemcpy(P.tab_buf.p, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+    return MI_OK;
+}
+
+int check_taps(const char* who, int taps) {
+    MI_REQUIRE(taps >= 2 && taps <= MI_PS_MAX_TAPS && taps % 2 == 0, "%s: wavelet of %d taps (an even number, 2 .. %d)", who, taps, MI_PS_MAX_TAPS);
+    return MI_OK;
+}
+
 int run_chunk(Plan& P, hipStream_t st, const void* in, const float* flat, void* out, int cnt) {
     const mi_pystripe_info& I = P.info;
     const mi_pystripe_params& q = P.prm;
@@ -956,7 +1206,8 @@ int run_chunk(Plan& P, hipStream_t st, const void* in, const float* flat, void* 
     else k.mode = OUT_FLOAT;
     k.flip = q.flip_upside_down; k.rot = q.rotate / 90;
     k.varies = varies;
-    if (!P.filter) {
+    if (!P.filter || I.levels == 0) {
+        if (P.filter) src.logp = 1;   // no wavelet level: the filter's result is log1p of the tile
         if (P.bleach) {
             src.logp = 1;   // L is log1p on load: no log image is written
             return run_bleach(P, st, src, k, cnt);
@@ -972,7 +1223,8 @@ int run_chunk(Plan& P, hipStream_t st, const void* in, const float* flat, void* 
         kL.tile_stride = (i64)P.sz_L;
         kL.log_out = 1;
     }
-    const int Lv = I.levels;
+    const int Lv = I.levels, LT = P.L;
+    const float* tab = P.tab_buf.as<float>();
     for (int pass = 0; pass < P.passes; ++pass) {
         // analysis
         for (int l = 1; l <= Lv; ++l) {
@@ -991,6 +1243,18 @@ int run_chunk(Plan& P, hipStream_t st, const void* in, const float* flat, void* 
                 rows = P.h[l - 1];
             }
             const int n = P.w[l - 1], m = P.w[l];
+            if (P.generic) {
+                hipLaunchKernelGGL(ana_rows_gen_kernel, dim3(cdiv(m, kRowBlock), rows, cnt), dim3(kRowBlock), 0, st, s, n, m, buf(P.off_rowL),
+                                   buf(P.off_rowH), (i64)P.sz_row, tab, LT);
+                MI_TRY(launch_check("ana_rows_gen_kernel"));
+                const size_t lds = (size_t)(2 * kColRows + LT - 2) * 64 * 2 * sizeof(float);
+                MI_TRY(raise_lds(reinterpret_cast<const void*>(&ana_cols_gen_kernel), lds));
+                hipLaunchKernelGGL(ana_cols_gen_kernel, dim3(cdiv(m, 64), cdiv(P.h[l], kColRows), cnt), dim3(256), lds, st, buf(P.off_rowL),
+                                   buf(P.off_rowH), (i64)P.sz_row, P.h[l - 1], P.h[l], m, map_pad, map_rows, map_mode, buf(P.off_A[l]),
+                                   (i64)P.sz_A[l], buf(P.off_cH[l]), buf(P.off_cV[l]), buf(P.off_cD[l]), (i64)P.sz_d[l], tab, LT);
+                MI_TRY(launch_check("ana_cols_gen_kernel"));
+                continue;
+            }
             hipLaunchKernelGGL(ana_rows_kernel, dim3(cdiv(m, kRowBlock), rows, cnt), dim3(kRowBlock), 0, st, s, n, m, buf(P.off_rowL),
                                buf(P.off_rowH), (i64)P.sz_row, P.f);
             MI_TRY(launch_check("ana_rows_kernel"));
@@ -1008,9 +1272,9 @@ int run_chunk(Plan& P, hipStream_t st, const void* in, const float* flat, void* 
         // synthesis, deepest level first; the reconstruction of level l lands in A[l - 1]'s buffer
         const bool last_pass = pass == P.passes - 1;
         for (int l = Lv; l >= 1; --l) {
-            const int m0 = P.h[l], m1 = P.w[l], s0 = 2 * m0 - 16, s1 = 2 * m1 - 16;
+            const int m0 = P.h[l], m1 = P.w[l], s0 = 2 * m0 - LT + 2, s1 = 2 * m1 - LT + 2;
             const float* a = buf(P.off_A[l]);
-            const int a_stride = l == Lv ? m1 : 2 * P.w[l + 1] - 16;
+            const int a_stride = l == Lv ? m1 : 2 * P.w[l + 1] - LT + 2;
             const bool fin = l == 1 && last_pass;
             int y0 = 0, y1 = s0, xp0 = 0, xp1 = s1 / 2;
             if (fin) {
@@ -1018,6 +1282,26 @@ int run_chunk(Plan& P, hipStream_t st, const void* in, const float* flat, void* 
                 xp0 = I.base_pad / 2; xp1 = (I.base_pad + I.nx + 1) / 2;
             }
             const int p0 = y0 / 2, p1 = (y1 + 1) / 2;
+            if (P.generic) {
+                const size_t lds = (size_t)(kColPairs + LT / 2 - 1) * 64 * 2 * sizeof(float);
+                MI_TRY(raise_lds(reinterpret_cast<const void*>(&syn_cols_gen_kernel), lds));
+                hipLaunchKernelGGL(syn_cols_gen_kernel, dim3(cdiv(m1, 64), cdiv(p1 - p0, kColPairs), 2 * cnt), dim3(256), lds, st, a, (i64)P.sz_A[l],
+                                   a_stride, buf(P.off_cH[l]), buf(P.off_cV[l]), buf(P.off_cD[l]), (i64)P.sz_d[l], m1, m0, p0, p1, s0,
+                                   buf(P.off_rowL), buf(P.off_rowH), (i64)P.sz_row, tab, LT);
+                MI_TRY(launch_check("syn_cols_gen_kernel"));
+                const dim3 grid(cdiv(xp1 - xp0, 256), y1 - y0, cnt);
+                if (fin) {
+                    hipLaunchKernelGGL(syn_rows_gen_kernel<true>, grid, dim3(256), 0, st, buf(P.off_rowL), buf(P.off_rowH), (i64)P.sz_row, m1, y0,
+                                       xp0, xp1, s1, (float*)nullptr, (i64)0, kL, tab, LT);
+                } else {
+                    float* dst = l == 1 ? buf(P.off_P) : buf(P.off_A[l - 1]);
+                    const i64 dst_stride = l == 1 ? (i64)P.sz_P : (i64)P.sz_A[l - 1];
+                    hipLaunchKernelGGL(syn_rows_gen_kernel<false>, grid, dim3(256), 0, st, buf(P.off_rowL), buf(P.off_rowH), (i64)P.sz_row, m1, y0,
+                                       xp0, xp1, s1, dst, dst_stride, kL, tab, LT);
+                }
+                MI_TRY(launch_check("syn_rows_gen_kernel"));
+                continue;
+            }
             hipLaunchKernelGGL(syn_cols_kernel, dim3(cdiv(m1, 64), cdiv(p1 - p0, 4), 2 * cnt), dim3(256), 0, st, a, (i64)P.sz_A[l], a_stride,
                                buf(P.off_cH[l]), buf(P.off_cV[l]), buf(P.off_cD[l]), (i64)P.sz_d[l], m1, p0, p1, s0, buf(P.off_rowL),
                                buf(P.off_rowH), (i64)P.sz_row, P.f);
@@ -1067,6 +1351,48 @@ extern "C" int mi_pystripe_plan_create(int dev, int ny, int nx, int in_dtype, co
     P->f = mi::make_filters();
     int rc = mi::derive(ny, nx, in_dtype, *params, *P);
     if (rc == MI_OK) rc = mi::build_tables(*P);
+    if (rc != MI_OK) {
+        delete P;
+        return rc;
+    }
+    *plan = P;
+    return MI_OK;
+}
+
+extern "C" int mi_pystripe_derive_wavelet(int ny, int nx, int in_dtype, const mi_pystripe_params* params, int taps, mi_pystripe_info* info) {
+    MI_REQUIRE(params && info, "mi_pystripe_derive_wavelet: null pointer");
+    MI_TRY(mi::check_taps("mi_pystripe_derive_wavelet", taps));
+    Plan P;
+    P.L = taps;
+    P.generic = true;
+    MI_TRY(mi::derive(ny, nx, in_dtype, *params, P));
+    *info = P.info;
+    return MI_OK;
+}
+
+extern "C" int mi_pystripe_plan_create_wavelet(int dev, int ny, int nx, int in_dtype, const mi_pystripe_params* params, const double* rec_lo,
+                                               int taps, void** plan) {
+    MI_REQUIRE(params && plan && rec_lo, "mi_pystripe_plan_create_wavelet: null pointer");
+    *plan = nullptr;
+    MI_TRY(mi::check_taps("mi_pystripe_plan_create_wavelet", taps));
+    // orthonormal under double shifts: what the quadrature-mirror construction of the other three filters needs
+    for (int i = 0; i < taps; ++i) MI_REQUIRE(std::isfinite(rec_lo[i]), "mi_pystripe_plan_create_wavelet: rec_lo[%d] is not finite", i);
+    double worst = 0.0;
+    for (int k = 0; 2 * k < taps; ++k) {
+        double sum = 0.0;
+        for (int i = 0; i + 2 * k < taps; ++i) sum += rec_lo[i] * rec_lo[i + 2 * k];
+        worst = std::max(worst, std::fabs(sum - (k == 0 ? 1.0 : 0.0)));
+    }
+    MI_REQUIRE(worst <= 1e-6, "mi_pystripe_plan_create_wavelet: rec_lo is not the low-pass of an orthogonal wavelet (residual %g, allowed 1e-6)",
+               worst);
+    MI_TRY(mi::use_device(dev));
+    Plan* P = new Plan;
+    P->dev = dev;
+    P->L = taps;
+    P->generic = true;
+    int rc = mi::derive(ny, nx, in_dtype, *params, *P);
+    if (rc == MI_OK) rc = mi::build_tables(*P);
+    if (rc == MI_OK) rc = mi::upload_filter_table(*P, rec_lo);
     if (rc != MI_OK) {
         delete P;
         return rc;

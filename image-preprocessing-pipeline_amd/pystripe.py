@@ -12,7 +12,9 @@ an error.
 
 What is computed (reference line numbers in include/mi_pystripe.h): uniform tile -> zeros; flat field; ``down_sample`` (max / min /
 mean, zero-padded blocks like skimage's ``block_reduce``); ``filter_streaks`` = log1p, numpy padding (reflect / wrap / symmetric /
-edge), db9 wavelet decomposition, the packed-position Gaussian notch on cH (and cV when ``bidirectional``), reconstruction, crop,
+edge), wavelet decomposition (``wavelet=``: 'db9', the pipeline's choice; 'haar' / 'db1' .. 'db20'; or any orthogonal wavelet of up
+to 128 taps as an object with ``rec_lo`` -- ``pywt.Wavelet("coif15")`` -- or the coefficients themselves; ``wavelets.py``), the
+packed-position Gaussian notch on cH (and cV when ``bidirectional``), reconstruction, crop,
 bleach correction (``bleach_correction_frequency`` with the three clips given, in log1p units: the log-domain image divided by a
 zero-phase first-order Butterworth low-pass of its clipped copy -- row by row, or, with ``bleach_correction_max_method``, the outer
 product of the filtered row and column maxima -- and rescaled by that copy's maximum; it also runs alone, at ``sigma=(0, 0)``),
@@ -27,7 +29,8 @@ Departures, all stated in INTEGRATION.md:
     zeros for a uniform such tile and divides by zero otherwise);
   * refused by name: ``bleach_correction_frequency`` without all three clips (the automatic ones need ``threshold_multiotsu``),
     ``enable_masking``, ``exclude_dark_edges_set_them_to_zero``,
-    ``new_size``, ``.dcimg`` input, ``down_sample_method='median'``, wavelets other than ``db9``, other padding modes, a ``threshold``
+    ``new_size``, ``.dcimg`` input, ``down_sample_method='median'``, a wavelet NAME without a built-in table (``'coif15'``: hand in
+    the coefficients instead), biorthogonal wavelets, other padding modes, a ``threshold``
     (``use_thresholding`` is never set on this path; ``crossover`` has no effect there either);
   * accepted and ignored: ``workers``, ``threads_per_gpu``, ``timeout``, ``gpu_semaphore``, ``z_step``, ``print_input_file_names``,
     ``verbose``.
@@ -51,7 +54,7 @@ if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     __package__ = "ipp_amd"
 
-from . import capi  # noqa: E402
+from . import capi, wavelets  # noqa: E402
 
 _NP_CODES = {np.dtype(np.uint8): capi.PS_U8, np.dtype(np.uint16): capi.PS_U16, np.dtype(np.float32): capi.PS_F32}
 _CODE_NP = {v: k for k, v in _NP_CODES.items()}
@@ -178,6 +181,15 @@ def _sigma_pair(sigma):
     return float(first), float(second)
 
 
+def _early_wavelet(sigma, wavelet):
+    """``wavelet`` as make_params will take it, resolved from the values alone before anything touches the device: "db9" stays the
+    name (the library's own route), everything else becomes its OrthogonalWavelet or raises.  Without a filter nothing is looked at."""
+    if _sigma_pair(sigma) > (0, 0):
+        found = wavelets.resolve(wavelet)
+        return "db9" if found is None else found
+    return wavelet
+
+
 def _dtype_code(dt, what):
     dt = np.dtype(dt)
     if dt not in _NP_CODES:
@@ -193,9 +205,9 @@ def make_params(in_dtype, flat=False, down_sample=None, down_sample_method="max"
     """mi_pystripe_params for process_img's options.  Everything the C side cannot name itself is refused here."""
     s1, s2 = _sigma_pair(sigma)
     filt = (s1, s2) > (0, 0)
+    wobj = None
     if filt:
-        if wavelet != "db9":
-            _refuse("wavelet", wavelet, "only 'db9' is built (the pipeline's choice)")
+        wobj = wavelets.resolve(wavelet)   # None: 'db9', the library's own 18-tap kernels
         if (s1 > 0) != (s2 > 0) or s1 < 0 or s2 < 0:
             raise ValueError(f"np_notch: sigma must be positive (sigma={sigma!r})")
         mode = padding_mode.lower() if isinstance(padding_mode, str) else padding_mode
@@ -246,13 +258,33 @@ def make_params(in_dtype, flat=False, down_sample=None, down_sample_method="max"
         p.bleach_frequency = float(bleach_correction_frequency)
         p.bleach_clip_min, p.bleach_clip_med, p.bleach_clip_max = (float(clips[name]) for name in BLEACH_CLIPS)
         p.bleach_max_method = int(bool(bleach_correction_max_method))
+    p.wavelet = wobj   # a Python attribute beside the C fields: None, or the OrthogonalWavelet that derive / Plan hand to the C side
     return p
+
+
+def orthogonal_wavelet(rec_lo, name=None):
+    """The small immutable object ``wavelet=`` stands for inside (``wavelets.OrthogonalWavelet``), from the reconstruction low-pass
+    coefficients -- what ``pywt.Wavelet(name).rec_lo`` holds.  ValueError naming ``wavelet`` when they are not an orthogonal wavelet
+    of 2 .. 128 taps."""
+    return wavelets.orthogonal_wavelet(rec_lo, name)
+
+
+def plan_key(shape, in_dtype, params):
+    """What identifies a plan: shape, dtype, every field of ``params`` and the wavelet's coefficient VALUES (two objects with equal
+    coefficients give equal keys; the object's identity and name do not enter)."""
+    w = getattr(params, "wavelet", None)
+    return (int(shape[0]), int(shape[1])), np.dtype(in_dtype).name, bytes(params), None if w is None else w.rec_lo
 
 
 def derive(shape, in_dtype, params):
     """The bookkeeping of a plan without a device (pad, padded shape, levels, coefficient shapes, output shape and type)."""
     info = capi.PystripeInfo()
-    capi.check(capi.lib().mi_pystripe_derive(int(shape[0]), int(shape[1]), _dtype_code(in_dtype, "dtype"), C.byref(params), C.byref(info)))
+    w = getattr(params, "wavelet", None)
+    args = (int(shape[0]), int(shape[1]), _dtype_code(in_dtype, "dtype"), C.byref(params))
+    if w is None:
+        capi.check(capi.lib().mi_pystripe_derive(*args, C.byref(info)))
+    else:
+        capi.check(capi.lib().mi_pystripe_derive_wavelet(*args, w.taps, C.byref(info)))
     return info
 
 
@@ -265,8 +297,13 @@ class Plan:
         self.device = torch.device(device if device is not None else "cuda:0")
         self.shape, self.in_dtype, self.params = (int(shape[0]), int(shape[1])), np.dtype(in_dtype), params
         self._h = C.c_void_p()
-        capi.check(capi.lib().mi_pystripe_plan_create(self.device.index or 0, self.shape[0], self.shape[1], _dtype_code(in_dtype, "dtype"),
-                                                      C.byref(params), C.byref(self._h)))
+        self.wavelet = getattr(params, "wavelet", None)
+        args = (self.device.index or 0, self.shape[0], self.shape[1], _dtype_code(in_dtype, "dtype"), C.byref(params))
+        if self.wavelet is None:
+            capi.check(capi.lib().mi_pystripe_plan_create(*args, C.byref(self._h)))
+        else:
+            rec_lo = (C.c_double * self.wavelet.taps)(*self.wavelet.rec_lo)
+            capi.check(capi.lib().mi_pystripe_plan_create_wavelet(*args, rec_lo, self.wavelet.taps, C.byref(self._h)))
         self.info = capi.PystripeInfo()
         capi.check(capi.lib().mi_pystripe_plan_info(self._h, C.byref(self.info)))
         self.out_shape = (self.info.out_ny, self.info.out_nx)
@@ -593,6 +630,7 @@ def filter_streaks(img, sigma=(250, 250), level=0, wavelet="db9", crossover=10, 
     s1, s2 = _sigma_pair(sigma)
     if s1 == s2 == 0 and bleach_correction_frequency is None:
         return img
+    wavelet = _early_wavelet((s1, s2), wavelet)
     bleach = _bleach_opts(img.shape, None, bleach_correction_frequency, bleach_correction_max_method, bleach_correction_clip_min,
                           bleach_correction_clip_med, bleach_correction_clip_max)
     return _run_tiles(img, None, device, sigma=(s1, s2), level=level, wavelet=wavelet, padding_mode=padding_mode, bidirectional=bidirectional,
@@ -606,8 +644,9 @@ def process_img(img, flat=None, gaussian_filter_2d=False, down_sample=None, down
                 bleach_correction_max_method=False, log1p_normalization_needed=True, dark=0, lightsheet=False, artifact_length=150,
                 background_window_size=200, percentile=0.25, lightsheet_vs_background=2.0, rotate=0, flip_upside_down=False,
                 convert_to_16bit=False, convert_to_8bit=False, bit_shift_to_right=8, d_type=None, verbose=False, device=None):
-    """pystripe/core.py:1190 on the GPU, the reference's keywords and defaults (so ``wavelet`` must be given as 'db9' when ``sigma`` asks
-    for the filter).  ``gaussian_filter_2d`` does nothing, as in the reference, whose GaussianBlur result is discarded.  ``img`` may be
+    """pystripe/core.py:1190 on the GPU, the reference's keywords and defaults (so ``wavelet`` must be given when ``sigma`` asks for the
+    filter: the default NAME 'coif15' has no table here; ``wavelet=pywt.Wavelet("coif15")`` or its ``rec_lo`` is taken).
+    ``gaussian_filter_2d`` does nothing, as in the reference, whose GaussianBlur result is discarded.  ``img`` may be
     a stack [n, ny, nx] of equally shaped tiles (an addition): they go through every launch together.  ``lightsheet=True`` runs
     ``correct_lightsheet`` after ``dark`` as the reference does; a tile too small for one window is refused from its shape alone.
     ``bleach_correction_frequency`` needs the three clips, in log1p units (the automatic ones are not built)."""
@@ -615,6 +654,7 @@ def process_img(img, flat=None, gaussian_filter_2d=False, down_sample=None, down
                             bleach_correction_clip_med=bleach_correction_clip_med, bleach_correction_clip_max=bleach_correction_clip_max,
                             new_size=new_size, exclude_dark_edges_set_them_to_zero=exclude_dark_edges_set_them_to_zero, threshold=threshold,
                             log1p_normalization_needed=log1p_normalization_needed))
+    wavelet = _early_wavelet(sigma, wavelet)
     ls = _lightsheet_opts(lightsheet, img.shape, down_sample, artifact_length, background_window_size, percentile, lightsheet_vs_background)
     bleach = _bleach_opts(img.shape, down_sample, bleach_correction_frequency, bleach_correction_max_method, bleach_correction_clip_min,
                           bleach_correction_clip_med, bleach_correction_clip_max)
@@ -734,6 +774,7 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
     bleach_args = (bleach_correction_frequency, bleach_correction_max_method, bleach_correction_clip_min, bleach_correction_clip_med,
                    bleach_correction_clip_max)
     _bleach_opts((7, 7), None, *bleach_args)   # the values alone; every tile shape is checked when it is met
+    wavelet = _early_wavelet(sigma, wavelet)
     input_path, output_path = Path(input_path), Path(output_path)
     if input_path.suffix.lower() == ".dcimg":
         _refuse("input_path", str(input_path), ".dcimg input is not built")
@@ -832,7 +873,8 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
             use_flat = flat is not None and flat.shape == shape
             if flat is not None and not use_flat:
                 print("warning: image and flat arrays had different shapes")
-            key = (shape, dt, use_flat)
+            # an OrthogonalWavelet compares and hashes by its coefficient values (without a filter the argument is not looked at)
+            key = (shape, dt, use_flat, wavelet if isinstance(wavelet, (str, wavelets.OrthogonalWavelet)) else None)
             if key not in plans:
                 _bleach_opts(shape, down_sample, *bleach_args)
                 ls = _lightsheet_opts(lightsheet, shape, down_sample, artifact_length, background_window_size, percentile,
@@ -891,7 +933,11 @@ def _parse_args(argv=None):
     p.add_argument("--sigma1", "-s1", type=float, default=0, help="foreground bandwidth [pixels]")
     p.add_argument("--sigma2", "-s2", type=float, default=0, help="background bandwidth [pixels]")
     p.add_argument("--level", "-l", type=int, default=0)
-    p.add_argument("--wavelet", default="db9")
+    which = p.add_mutually_exclusive_group()
+    which.add_argument("--wavelet", default="db9", help="'db9' (default), 'haar' or 'db1' .. 'db20'")
+    which.add_argument("--wavelet_file", default=None, metavar="FILE",
+                       help="any other orthogonal wavelet of up to 128 taps: its reconstruction low-pass (PyWavelets' rec_lo) as a .npy file "
+                            "or a text file of numbers")
     p.add_argument("--threshold", type=float, default=None)
     p.add_argument("--crossover", type=float, default=10)
     p.add_argument("--padding_mode", default="reflect")
@@ -949,6 +995,11 @@ def _estimated_clips(a, estimate=None):
     return clips
 
 
+def _cli_wavelet(a):
+    """``wavelet=`` of the command line: the name, or the coefficients of --wavelet_file."""
+    return wavelets.load_file(a.wavelet_file) if a.wavelet_file else a.wavelet
+
+
 def main(argv=None):
     a = _parse_args(argv)
     inp = Path(a.input)
@@ -961,7 +1012,7 @@ def main(argv=None):
     clips = _estimated_clips(a)
     stats = {}
     rc = batch_filter(inp, out, flat=flat, gaussian_filter_2d=a.gaussian_filter_2d, sigma=(a.sigma1, a.sigma2), level=a.level,
-                      wavelet=a.wavelet, crossover=a.crossover, threshold=a.threshold, padding_mode=a.padding_mode,
+                      wavelet=_cli_wavelet(a), crossover=a.crossover, threshold=a.threshold, padding_mode=a.padding_mode,
                       bidirectional=a.bidirectional, bleach_correction_frequency=a.bleach_correction_frequency,
                       bleach_correction_max_method=a.bleach_correction_max_method, dark=a.dark, rotate=a.rotate, flip_upside_down=a.flip_upside_down,
                       lightsheet=a.lightsheet, artifact_length=a.artifact_length, background_window_size=a.background_window_size,

@@ -7,15 +7,18 @@
  *                                       integer tiles)
  *   correct_bleaching      :501-559, butter_lowpass_filter :492-498  (with explicit clips; see "Bleach correction" below)
  *   filter_streak_dual_band:943-979    (sigma1 == sigma2: one filter_subband; else one after the other)
- *   filter_subband         :927-940    (numpy branch: wavedec2 'symmetric' db9, np_filter_coefficient on cH and cV, waverec2)
+ *   filter_subband         :927-940    (numpy branch: wavedec2 'symmetric', np_filter_coefficient on cH and cV, waverec2; db9 by
+ *                                       mi_pystripe_plan_create, any orthogonal wavelet of up to MI_PS_MAX_TAPS taps by
+ *                                       mi_pystripe_plan_create_wavelet; see "Wavelets" below)
  *   np_filter_coefficient  :749-754, np_notch :637-667  (gains applied by PACKED position of scipy.fftpack.rfft's real spectrum)
  *   calculate_pad_size     :681-698, notch_rise_point :670-678, convert_to_8bit_fun :402-425, convert_to_16bit_fun :397-399,
  *   is_uniform_2d          :107-121,  calculate_down_sampled_size :1162-1170
  * skimage.measure.block_reduce (zero padding to a multiple of the block) is restated for max / min / mean.
  *
  * Not built (refused by the Python layer by name): the automatic bleach-correction clips (threshold_multiotsu), masking, dark-edge
- * exclusion, new_size, wavelets other than db9, padding modes other than reflect / wrap / symmetric / edge, the median
- * down-sampling.  The lightsheet correction of process_img :1333-1348 is mi_lightsheet.h; the Python layer runs it between two
+ * exclusion, new_size, biorthogonal wavelets and wavelets named without a table (the library holds the Daubechies family only; the
+ * Python layer takes any other orthogonal wavelet as its coefficients), padding modes other than reflect / wrap / symmetric / edge,
+ * the median down-sampling.  The lightsheet correction of process_img :1333-1348 is mi_lightsheet.h; the Python layer runs it between two
  * plans of this header.
  *
  * Bleach correction (bleach_frequency > 0), on the float32 log-domain image L (the stripe filter's cropped result, or log1p(tile)
@@ -28,6 +31,17 @@
  *        max_method: the row maxima and column maxima of L go through the same clip and filter over their own length, and
  *        F[y][x] = ry[y] * cx[x] (a float32 product, never stored);
  *   L' = (L / F) * max(F) in float32, the maximum over the tile; then the tail as before.
+ *
+ * Wavelets.  A wavelet is its reconstruction low-pass rec_lo[L], L even; hi_r[t] = (-1)^t rec_lo[L - 1 - t] and the decomposition
+ * pair is the reversed reconstruction pair.  PyWavelets' wavedec2 / waverec2, mode 'symmetric': an extent n gives (n + L - 1) / 2
+ * coefficients, m coefficients reconstruct 2 m - L + 2 samples, and the automatic level (params.level == 0) is the minimum over both
+ * padded extents of floor(log2(n / (L - 1))), 0 when n < L - 1.  At level 0 the filter leaves the log image as it is (info.levels
+ * == 0; log1p, expm1 and everything behind them still run).  An explicit level beyond the automatic one is allowed: the symmetric
+ * extension then reflects more than once and a coefficient line may be as short as L / 2 samples.  The 34-sample minimum and
+ * calculate_pad_size do not depend on the wavelet.  Which kernels run is decided by the entry alone: mi_pystripe_plan_create runs
+ * the db9 kernels (18 taps unrolled, filters in scalar registers); mi_pystripe_plan_create_wavelet runs the kernels with a
+ * run-time tap count (filter table in device memory, column passes staged in LDS), also when rec_lo holds the 18 db9 values.
+ *
  * A row (or maxima vector) of n samples stays in LDS as n + 12 doubles while n <= MI_PS_BLEACH_LDS_ROW; a longer one goes through
  * LDS in segments with the carried filter state and a float64 scratch row for the forward result.
  */
@@ -44,13 +58,14 @@ typedef enum { MI_PS_U8 = 0, MI_PS_U16 = 1, MI_PS_F32 = 2 } mi_pystripe_dtype;
 typedef enum { MI_PS_REFLECT = 0, MI_PS_WRAP = 1, MI_PS_SYMMETRIC = 2, MI_PS_EDGE = 3 } mi_pystripe_padding;   /* numpy.pad modes */
 typedef enum { MI_PS_DOWN_MAX = 0, MI_PS_DOWN_MIN = 1, MI_PS_DOWN_MEAN = 2 } mi_pystripe_down;
 #define MI_PS_MAX_LEVELS 24
+#define MI_PS_MAX_TAPS 128
 /* bleach correction: the longest row whose n + 12 doubles fit the LDS of one work-group beside the 16 wave totals of the scan:
  * (160 KiB - 16 * 16 B) / 8 B - 12 */
 #define MI_PS_BLEACH_LDS_ROW 20436
 
 typedef struct {
     double sigma1, sigma2;     /* (0, 0): no stripe filter; both > 0 otherwise ("sigma must be positive", np_notch :654) */
-    int level;                 /* 0: min over both padded extents of floor(log2(n / 17)) */
+    int level;                 /* 0: min over both padded extents of floor(log2(n / (taps - 1))), taps = 18 for db9 */
     int padding_mode;          /* mi_pystripe_padding */
     int bidirectional;         /* also filter cV along axis -2 */
     int down_y, down_x;        /* block of down_sample (1: that axis is kept); both 0: no down_sample at all */
@@ -88,6 +103,12 @@ typedef struct {
 /* A plan for tiles of ny x nx samples of in_dtype on device dev.  Synchronises (uploads its tables).  A plan owns its scratch:
  * one thread and one stream use it at a time. */
 int mi_pystripe_plan_create(int dev, int ny, int nx, int in_dtype, const mi_pystripe_params* params, void** plan);
+/* as mi_pystripe_plan_create / _derive, for the orthogonal wavelet whose reconstruction low-pass is rec_lo[taps] (host memory,
+ * float64; the kernels use it as float32): taps even, 2 .. MI_PS_MAX_TAPS, every value finite, and
+ * max_k |sum_n rec_lo[n] rec_lo[n + 2 k] - delta_k| <= 1e-6, else MI_ERR_INVALID. */
+int mi_pystripe_plan_create_wavelet(int dev, int ny, int nx, int in_dtype, const mi_pystripe_params* params, const double* rec_lo, int taps,
+                                    void** plan);
+int mi_pystripe_derive_wavelet(int ny, int nx, int in_dtype, const mi_pystripe_params* params, int taps, mi_pystripe_info* info);
 int mi_pystripe_plan_destroy(void* plan);
 int mi_pystripe_plan_info(void* plan, mi_pystripe_info* info);
 /* The bookkeeping alone, without a device: what a plan for this shape would derive (scratch_bytes_per_tile included). */

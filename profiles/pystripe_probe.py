@@ -6,7 +6,12 @@
                                                          write), and a device copy of the same bytes
     python profiles/pystripe_probe.py trace [B]          one warm-up and one run of batch B at sigma (250, 250) -- for
                                                          rocprofv3 --kernel-trace --stats -- python3 profiles/pystripe_probe.py trace 8
-    python profiles/pystripe_probe.py e2e DIR [tiles]    `tiles` (default 256) deflate TIFF tiles of 2048 x 2048 uint16 under DIR/in,
+    python profiles/pystripe_probe.py wavelet [B ...]    sigma (250, 250) with "db9" by name, the 18 db9 coefficients (the kernels for any
+                                                         tap count) and a 90-tap orthonormal filter, batches B (default 32 1): ms per
+                                                         tile, five runs of the median of 5 and their spread
+    python profiles/pystripe_probe.py wavelet_trace K [B]  one warm-up and one run of choice K (0, 1, 2 in that order), batch B -- for
+                                                         rocprofv3 --kernel-trace --stats, which gives the wavelet passes' share
+    python profiles/pystripe_probe.py e2e DIR [tiles]   `tiles` (default 256) deflate TIFF tiles of 2048 x 2048 uint16 under DIR/in,
                                                          then batch_filter -> DIR/out: tiles/s and the read / compute / write seconds
     python profiles/pystripe_probe.py cpu                the numpy / scipy restatement of tests/pystripe_util.py on one tile (context
                                                          only: it is not the reference's implementation, which needs PyWavelets)
@@ -78,6 +83,53 @@ def kernel(batches):
           f"{mc / nb:.4f} ms per tile")
 
 
+def lattice_rec_lo(taps, seed=1):
+    """an orthonormal low-pass of any even length (the paraunitary lattice of tests/wavelet_util.py): stands in for coif15's 90 taps"""
+    from tests import wavelet_util as W
+    return W.lattice_filter(taps, seed)
+
+
+def wavelet_choices():
+    from ipp_amd import wavelets
+    return [("db9 by name (18-tap kernels)", "db9"), ("db9 as 18 coefficients (any-length kernels)", wavelets.daubechies(9)),
+            ("90 taps (any-length kernels)", lattice_rec_lo(90))]
+
+
+def wavelet(batches, runs=5):
+    """2048^2 uint16, sigma (250, 250), reflect, bidirectional: ms per tile for each wavelet choice; `runs` runs of the median-of-5
+    each, whose spread is the run-to-run spread.  The share of the wavelet passes comes from `wavelet_trace` under rocprofv3."""
+    import torch
+    from ipp_amd import pystripe as ps
+    dev = torch.device("cuda", 0)
+    tin = tiles_u16(max(batches), dev)
+    for label, w in wavelet_choices():
+        for b in batches:
+            prm = ps.make_params(np.uint16, sigma=(250, 250), max_batch=b, **dict(PIPE, wavelet=w))
+            plan = ps.Plan(dev, (NY, NX), np.uint16, prm)
+            out = torch.empty((b, NY, NX), dtype=torch.uint16, device=dev)
+            x = tin[:b].contiguous()
+            plan.run(x, out=out)
+            ms = [timed(lambda: plan.run(x, out=out)) / b for _ in range(runs)]
+            print(f"{label}, batch {b:3d}: {np.median(ms):7.3f} ms per tile (runs {' '.join(f'{v:.3f}' for v in ms)}; spread "
+                  f"{100 * (max(ms) - min(ms)) / np.median(ms):.1f} %), {plan.info.levels} levels")
+            plan.close()
+
+
+def wavelet_trace(which, b):
+    """one warm-up and one run of batch b with wavelet choice `which` (0, 1, 2 of wavelet_choices) -- for rocprofv3 --kernel-trace --stats"""
+    import torch
+    from ipp_amd import pystripe as ps
+    dev = torch.device("cuda", 0)
+    x = tiles_u16(b, dev)
+    label, w = wavelet_choices()[which]
+    plan = ps.Plan(dev, (NY, NX), np.uint16, ps.make_params(np.uint16, sigma=(250, 250), max_batch=b, **dict(PIPE, wavelet=w)))
+    for _ in range(2):
+        plan.run(x)
+    torch.cuda.synchronize()
+    plan.close()
+    print(label)
+
+
 def trace(b):
     import torch
     from ipp_amd import pystripe as ps
@@ -126,6 +178,10 @@ if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else "kernel"
     if mode == "kernel":
         kernel([int(v) for v in sys.argv[2:]] or [1, 8, 32])
+    elif mode == "wavelet":
+        wavelet([int(v) for v in sys.argv[2:]] or [32, 1])
+    elif mode == "wavelet_trace":
+        wavelet_trace(int(sys.argv[2]), int(sys.argv[3]) if len(sys.argv) > 3 else 32)
     elif mode == "trace":
         trace(int(sys.argv[2]) if len(sys.argv) > 2 else 8)
     elif mode == "e2e":
