@@ -250,6 +250,11 @@ SIGNATURES = {
     "mi_lightsheet_plan_info": (_i, [_vp, C.POINTER(LightsheetInfo)]),
     "mi_lightsheet_run": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64]),
     "mi_lightsheet_local_percentile": (_i, [_i, _vp, _vp, _i, _i, _i, C.c_int64] + [_i] * 6 + [C.c_double, _i, _vp, _i]),
+    # mi_tile_resize.h
+    "mi_tile_resize_tables": (_i, [_i, _i, _ip, _ip, C.POINTER(C.c_double)]),
+    "mi_tile_resize_plan_create": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
+    "mi_tile_resize_run": (_i, [_vp, _vp, _vp, _vp, C.c_int64]),
+    "mi_tile_resize_plan_destroy": (_i, [_vp]),
     # mi_isodown.h
     "mi_isodown_derive": (_i, [_i, _i, C.c_double, C.c_double, C.c_double, _i, C.POINTER(IsodownInfo)]),
     "mi_isodown_plan_create": (_i, [_i, _i, _i, _i, C.POINTER(IsodownParams), C.POINTER(_vp)]),

@@ -19,7 +19,8 @@ bleach correction (``bleach_correction_frequency`` with the three clips given, i
 zero-phase first-order Butterworth low-pass of its clipped copy -- row by row, or, with ``bleach_correction_max_method``, the outer
 product of the filtered row and column maxima -- and rescaled by that copy's maximum; it also runs alone, at ``sigma=(0, 0)``),
 expm1, rint + clip for integer tiles; ``dark``; ``lightsheet`` (pystripe/lightsheet_correct.py: local percentiles on two sub-grids,
-order-1 resampling, subtraction; include/mi_lightsheet.h); 8 / 16-bit conversion; flip; rotation.
+order-1 resampling, subtraction; include/mi_lightsheet.h); in ``batch_filter`` the resize to ``new_size`` (order-1 zoom and clip,
+include/mi_tile_resize.h; ``resize_tiles`` runs it alone); 8 / 16-bit conversion; flip; rotation.
 
 Departures, all stated in INTEGRATION.md:
   * ``flat`` on an integer tile: the reference's in-place divide raises; here the tile is divided in float32 and is a float tile from
@@ -29,7 +30,9 @@ Departures, all stated in INTEGRATION.md:
     zeros for a uniform such tile and divides by zero otherwise);
   * refused by name: ``bleach_correction_frequency`` without all three clips (the automatic ones need ``threshold_multiotsu``),
     ``enable_masking``, ``exclude_dark_edges_set_them_to_zero``,
-    ``new_size``, ``.dcimg`` input, ``down_sample_method='median'``, a wavelet NAME without a built-in table (``'coif15'``: hand in
+    ``new_size`` in ``process_img`` (``batch_filter`` takes it), a ``new_size`` that needs skimage's Gaussian pre-filter (the tile
+    shape below ``new_size`` as tuples with an axis that shrinks) or meets an integer tile with a float ``d_type``, ``.dcimg`` input,
+    ``down_sample_method='median'``, a wavelet NAME without a built-in table (``'coif15'``: hand in
     the coefficients instead), biorthogonal wavelets, other padding modes, a ``threshold``
     (``use_thresholding`` is never set on this path; ``crossover`` has no effect there either);
   * accepted and ignored: ``workers``, ``threads_per_gpu``, ``timeout``, ``gpu_semaphore``, ``z_step``, ``print_input_file_names``,
@@ -127,7 +130,7 @@ def _check_unsupported(kw):
         if kw.get(name):
             _refuse(name, kw[name], "not built (needs OpenCV / scikit-image semantics)")
     if kw.get("new_size") is not None:
-        _refuse("new_size", kw["new_size"], "skimage.transform.resize is not built")
+        _refuse("new_size", kw["new_size"], "process_img does not resize; batch_filter (and resize_tiles) do")
     if kw.get("threshold") is not None:
         _refuse("threshold", kw["threshold"], "the thresholding dual-band path is not built")
     if kw.get("log1p_normalization_needed") is False:
@@ -534,16 +537,118 @@ def correct_lightsheet(img, percentile=0.25, mask=None, lightsheet=dict(selem=(1
     return got[0] if len(got) == 1 else tuple(got)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# resize to new_size (pystripe/core.py:1356-1359; include/mi_tile_resize.h)
+
+def check_new_size(new_size):
+    """``new_size`` as a tuple of two positive Python integers, or ValueError naming it."""
+    try:
+        pair = tuple(new_size)
+    except TypeError:
+        pair = ()
+    ok = len(pair) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and v >= 1 for v in pair)
+    if not ok:
+        raise ValueError(f"new_size={new_size!r}: two positive integers (rows, columns) are expected")
+    return int(pair[0]), int(pair[1])
+
+
+def resize_decision(tile_shape, new_size):
+    """What process_img does with a tile of ``tile_shape`` (after ``down_sample``) for ``new_size``, from the shapes alone: None when
+    nothing is resized (no ``new_size``, or equal shapes), else ``new_size`` as a tuple.  The reference compares the two shapes as
+    tuples: below ``new_size`` it resizes with ``anti_aliasing=True``, above it without.  The Gaussian pre-filter of the first case
+    acts on an axis that shrinks only; that mixed case is refused (NotImplementedError naming ``new_size``), every other one is the
+    plain order-1 zoom."""
+    if new_size is None:
+        return None
+    N = check_new_size(new_size)
+    T = (int(tile_shape[-2]), int(tile_shape[-1]))
+    if T == N:
+        return None
+    if T < N and (N[0] < T[0] or N[1] < T[1]):
+        _refuse("new_size", N, f"a tile of shape {T} is below it as a tuple, so the reference resizes with anti_aliasing=True, and an axis "
+                               "shrinks: the Gaussian pre-filter on float64 is not built")
+    return N
+
+
+def tile_resize_tables(n, m):
+    """(i0, i1, t) of one axis of the resize, n samples -> m samples, from the library's own host function (no device needed)."""
+    i0, i1, t = np.empty(m, np.int32), np.empty(m, np.int32), np.empty(m, np.float64)
+    capi.check(capi.lib().mi_tile_resize_tables(int(n), int(m), i0.ctypes.data_as(C.POINTER(C.c_int)), i1.ctypes.data_as(C.POINTER(C.c_int)),
+                                                t.ctypes.data_as(C.POINTER(C.c_double))))
+    return i0, i1, t
+
+
+class ResizePlan:
+    """mi_tile_resize plan for tiles of one shape and dtype.  ``run(tiles)``: [n, ny, nx] device tensor -> [n, my, mx] of the same type."""
+
+    def __init__(self, device, shape, new_size, dtype, max_batch=0):
+        import torch
+        self.shape, self.out_shape, self.dtype = (int(shape[0]), int(shape[1])), check_new_size(new_size), np.dtype(dtype)
+        code = _dtype_code(dtype, "dtype")
+        capi.require_gpu()
+        self.device = torch.device(device if device is not None else "cuda:0")
+        self._h = C.c_void_p()
+        capi.check(capi.lib().mi_tile_resize_plan_create(self.device.index or 0, self.shape[0], self.shape[1], self.out_shape[0], self.out_shape[1],
+                                                         code, int(max_batch), C.byref(self._h)))
+
+    def run(self, tiles, out=None):
+        import torch
+        tdt = getattr(torch, self.dtype.name)
+        if not (isinstance(tiles, torch.Tensor) and tiles.is_cuda and tiles.is_contiguous() and tiles.dim() == 3 and tiles.dtype == tdt
+                and tuple(tiles.shape[1:]) == self.shape):
+            raise ValueError(f"ResizePlan.run: a contiguous [n, {self.shape[0]}, {self.shape[1]}] {self.dtype.name} device tensor is expected")
+        n = int(tiles.shape[0])
+        if out is None:
+            out = torch.empty((n,) + self.out_shape, dtype=tdt, device=tiles.device)
+        elif tuple(out.shape) != (n,) + self.out_shape or out.dtype != tdt or not out.is_contiguous() or out.device != tiles.device:
+            raise ValueError("ResizePlan.run: out must be a contiguous tensor of the result's shape and the input's type")
+        with torch.cuda.device(tiles.device):
+            capi.check(capi.lib().mi_tile_resize_run(self._h, capi.current_stream_ptr(tiles.device), tiles.data_ptr(), out.data_ptr(), n))
+        return out
+
+    def close(self):
+        if self._h:
+            capi.lib().mi_tile_resize_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def resize_tiles(img, new_size, device=None):
+    """``skimage.transform.resize(img, new_size, preserve_range=True, anti_aliasing=False)`` as process_img uses it
+    (pystripe/core.py:1359) on the GPU: scipy's order-1 zoom (mode 'mirror', grid_mode) and a clip to the tile's own [min, max].
+    ``img``: a 2-D tile or a stack [n, ny, nx], numpy or device tensor, uint8 / uint16 / float32; the same container and dtype come
+    back (an integer tile is the truncated float64 result, which is what process_img's astype makes of it)."""
+    import torch
+    N = check_new_size(new_size)
+    tiles, single, is_tensor, in_dtype = _as_stack(img, device)
+    plan = ResizePlan(tiles.device, tuple(int(v) for v in tiles.shape[1:]), N, in_dtype, max_batch=min(int(tiles.shape[0]), 16))
+    try:
+        out = plan.run(tiles)
+        torch.cuda.synchronize(tiles.device)
+    finally:
+        plan.close()
+    out = out[0] if single else out
+    return out if is_tensor else out.cpu().numpy()
+
+
 class Pipeline:
     """process_img for tiles of one shape and dtype: one pystripe plan, or -- with ``lightsheet`` (a dict of artifact_length,
-    background_window_size, percentile, lightsheet_vs_background) -- three steps that stay on the device: the pystripe plan up to and
-    including ``dark`` in the tile's own kind, the lightsheet plan in place, and a filter-less pystripe plan for conversion, flip
-    and rotation (left out when it would change nothing)."""
+    background_window_size, percentile, lightsheet_vs_background) or a ``new_size`` that differs from the tile's shape after
+    ``down_sample`` -- up to four steps that stay on the device: the pystripe plan up to and including ``dark`` in the tile's own
+    kind, the lightsheet plan in place, the resize plan, and a filter-less pystripe plan for conversion, flip and rotation (left
+    out when it would change nothing).  A uniform tile leaves the first step as zeros and stays zeros through the others."""
 
-    def __init__(self, device, shape, in_dtype, flat=False, lightsheet=None, max_batch=0, **opts):
+    def __init__(self, device, shape, in_dtype, flat=False, lightsheet=None, new_size=None, max_batch=0, **opts):
         in_dtype = np.dtype(in_dtype)
-        self.tail = self.ls = None
-        if lightsheet is None:
+        self.tail = self.ls = self.resize = None
+        down = opts.get("down_sample")
+        resize_to = resize_decision(shape if down is None else calculate_down_sampled_size(shape, down), new_size)
+        if lightsheet is None and resize_to is None:
             self.head = Plan(device, shape, in_dtype, make_params(in_dtype, flat=flat, max_batch=max_batch, **opts))
             return
         tail_names = ("rotate", "flip_upside_down", "convert_to_16bit", "convert_to_8bit", "bit_shift_to_right")
@@ -554,16 +659,26 @@ class Pipeline:
         mid_type = in_dtype if info.integer_kind else np.dtype(np.float32)   # the kind the tile has after ``dark``
         prm.out_dtype = _dtype_code(mid_type, "dtype")
         mid_shape = (info.ny, info.nx)
-        check_lightsheet_shape(mid_shape, lightsheet.get("artifact_length", 150))
-        ls_prm = make_lightsheet_params(entry_type, max_batch=max_batch, **lightsheet)
+        ls_prm = None
+        if lightsheet is not None:
+            check_lightsheet_shape(mid_shape, lightsheet.get("artifact_length", 150))
+            ls_prm = make_lightsheet_params(entry_type, max_batch=max_batch, **lightsheet)
+        tail_shape = mid_shape if resize_to is None else resize_to
         tail_prm = make_params(mid_type, max_batch=max_batch, keep_uniform=True, d_type=entry_type, **{k: opts[k] for k in tail_names if k in opts})
-        tail_info = derive(mid_shape, mid_type, tail_prm)
+        tail_info = derive(tail_shape, mid_type, tail_prm)
+        out_type = _CODE_NP[tail_info.out_dtype]
+        if resize_to is not None and mid_type.kind == "u" and out_type.kind == "f":
+            _refuse("new_size", resize_to, f"a {mid_type.name} tile with d_type={out_type.name}: the reference keeps the fractions of the "
+                                           "float64 image there; the resize of an integer tile is built with the truncation that follows it")
         self.head = Plan(device, shape, in_dtype, prm)
         try:
-            self.ls = LightsheetPlan(device, mid_shape, mid_type, ls_prm)
-            changes = tail_prm.rotate or tail_prm.flip_upside_down or _CODE_NP[tail_info.out_dtype] != mid_type
+            if ls_prm is not None:
+                self.ls = LightsheetPlan(device, mid_shape, mid_type, ls_prm)
+            if resize_to is not None:
+                self.resize = ResizePlan(device, mid_shape, resize_to, mid_type, max_batch=max_batch)
+            changes = tail_prm.rotate or tail_prm.flip_upside_down or out_type != mid_type
             if changes:
-                self.tail = Plan(device, mid_shape, mid_type, tail_prm)
+                self.tail = Plan(device, tail_shape, mid_type, tail_prm)
         except Exception:
             self.close()
             raise
@@ -572,12 +687,14 @@ class Pipeline:
         out = self.head.run(tiles, flat)
         if self.ls is not None:
             self.ls.run(out)
+        if self.resize is not None:
+            out = self.resize.run(out)
         if self.tail is not None:
             out = self.tail.run(out)
         return out
 
     def close(self):
-        for plan in (self.head, self.ls, self.tail):
+        for plan in (self.head, self.ls, self.resize, self.tail):
             if plan is not None:
                 plan.close()
 
@@ -762,7 +879,9 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
     rank takes every WORLD_SIZE-th file on its LOCAL_RANK device.  ``continue_process``: a file whose output exists is skipped.  A file
     that cannot be read becomes a zero tile when ``d_type`` and ``tile_size`` are given, else it is skipped with a warning.
     ``bleach_correction_frequency`` needs the three clips, in log1p units; ``bleach_correction_max_method`` defaults to True here, as
-    in the reference.  ``workers``, ``threads_per_gpu``, ``timeout``, ``z_step``, ``print_input_file_names`` are accepted and ignored.  ``stats`` (a dict)
+    in the reference.  ``new_size``: every tile whose own shape after ``down_sample`` differs from it is resized to it after ``dark`` /
+    ``lightsheet`` and before the conversion (``resize_decision``, ``resize_tiles``); outputs have that shape, swapped under
+    ``rotate`` 90 / 270.  A tile whose shape differs from ``tile_size`` is not resized to ``tile_size``, as in the reference.  ``workers``, ``threads_per_gpu``, ``timeout``, ``z_step``, ``print_input_file_names`` are accepted and ignored.  ``stats`` (a dict)
     receives the seconds spent reading, computing and writing and the file counts."""
     import time
     import torch
@@ -770,8 +889,13 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
         raise TypeError("convert_to_16bit and convert_to_8bit are both set: choose one output format")
     _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, bleach_correction_clip_min=bleach_correction_clip_min,
                             bleach_correction_clip_med=bleach_correction_clip_med, bleach_correction_clip_max=bleach_correction_clip_max,
-                            new_size=new_size, threshold=threshold))
-    bleach_args = (bleach_correction_frequency, bleach_correction_max_method, bleach_correction_clip_min, bleach_correction_clip_med,
+                            threshold=threshold))
+    if new_size is not None:   # the values, and the shapes where they are known, before anything touches the device
+        new_size = check_new_size(new_size)
+        if tile_size is not None:
+            known = tuple(int(v) for v in tile_size)
+            resize_decision(known if down_sample is None else calculate_down_sampled_size(known, down_sample), new_size)
+    bleach_args =(bleach_correction_frequency, bleach_correction_max_method, bleach_correction_clip_min, bleach_correction_clip_med,
                    bleach_correction_clip_max)
     _bleach_opts((7, 7), None, *bleach_args)   # the values alone; every tile shape is checked when it is met
     wavelet = _early_wavelet(sigma, wavelet)
@@ -879,7 +1003,7 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
                 _bleach_opts(shape, down_sample, *bleach_args)
                 ls = _lightsheet_opts(lightsheet, shape, down_sample, artifact_length, background_window_size, percentile,
                                       lightsheet_vs_background)
-                plans[key] = (Pipeline(device, shape, dt, flat=use_flat, lightsheet=ls, max_batch=chunk, **opts),
+                plans[key] = (Pipeline(device, shape, dt, flat=use_flat, lightsheet=ls, new_size=new_size, max_batch=chunk, **opts),
                               torch.from_numpy(flat).to(device) if use_flat else None)
             plan, flat_t = plans[key]
             stack = torch.from_numpy(np.stack([m[0] for m in members])).to(device)
@@ -897,7 +1021,7 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
         if first is not None and first.ndim == 2 and first.dtype in _NP_CODES:
             _bleach_opts(first.shape, down_sample, *bleach_args)
             info = derive(first.shape, first.dtype, make_params(first.dtype, flat=False, **opts))
-            per_tile = info.scratch_bytes_per_tile + 2 * first.size * 4
+            per_tile = info.scratch_bytes_per_tile + 2 * first.size * 4 + (2 * new_size[0] * new_size[1] * 4 if new_size else 0)
             with torch.cuda.device(device):
                 free = torch.cuda.mem_get_info()[0]
             chunk = int(min(max(free // 4 // max(per_tile, 1), 1), 64))
@@ -964,6 +1088,8 @@ def _parse_args(argv=None):
     p.add_argument("--continue_process", action="store_true")
     p.add_argument("--dtype", default=None)
     p.add_argument("--tile_size", type=int, nargs=2, default=None, metavar=("NY", "NX"))
+    p.add_argument("--size_y", type=int, default=None, help="new image size in Y axis (with --size_x): every tile is resized to it")
+    p.add_argument("--size_x", type=int, default=None, help="new image size in X axis (with --size_y)")
     p.add_argument("--gaussian_filter_2d", action="store_true", help="accepted; does nothing, as in the reference")
     p.add_argument("--max_batch", type=int, default=None, help="tiles per launch (default: from the free device memory)")
     p.add_argument("--bleach_correction_frequency", type=float, default=None,
@@ -1000,8 +1126,17 @@ def _cli_wavelet(a):
     return wavelets.load_file(a.wavelet_file) if a.wavelet_file else a.wavelet
 
 
+def _cli_new_size(a):
+    """``new_size=`` of the command line: (--size_y, --size_x), None without both; one alone is the reference's error."""
+    if (a.size_y is None) != (a.size_x is None):
+        print("both new_size_x and new_size_y are needed!")
+        raise RuntimeError("both new_size_x and new_size_y are needed! (--size_y and --size_x go together)")
+    return None if a.size_y is None else (a.size_y, a.size_x)
+
+
 def main(argv=None):
     a = _parse_args(argv)
+    new_size = _cli_new_size(a)
     inp = Path(a.input)
     out = Path(a.output) if a.output else inp.parent / (inp.name + "_destriped")
     flat = None
@@ -1019,7 +1154,7 @@ def main(argv=None):
                       percentile=a.percentile, lightsheet_vs_background=a.lightsheet_vs_background, convert_to_16bit=a.convert_to_16bit, convert_to_8bit=a.convert_to_8bit,
                       bit_shift_to_right=a.bit_shift_to_right, continue_process=a.continue_process, d_type=a.dtype,
                       tile_size=tuple(a.tile_size) if a.tile_size else None, down_sample=tuple(a.down_sample) if a.down_sample else None,
-                      down_sample_method=a.down_sample_method, compression=(a.compression_method, a.compression_level),
+                      new_size=new_size, down_sample_method=a.down_sample_method, compression=(a.compression_method, a.compression_level),
                       max_batch=a.max_batch, stats=stats, **clips)
     print("pystripe: {files} files, {written} written, {skipped_existing} already there, {skipped_unreadable} unreadable, "
           "{zero_tiles} zero tiles; read {read_s:.2f} s, compute {compute_s:.2f} s, write {write_s:.2f} s".format(**stats))

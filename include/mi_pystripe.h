@@ -16,10 +16,11 @@
  * skimage.measure.block_reduce (zero padding to a multiple of the block) is restated for max / min / mean.
  *
  * Not built (refused by the Python layer by name): the automatic bleach-correction clips (threshold_multiotsu), masking, dark-edge
- * exclusion, new_size, biorthogonal wavelets and wavelets named without a table (the library holds the Daubechies family only; the
+ * exclusion, biorthogonal wavelets and wavelets named without a table (the library holds the Daubechies family only; the
  * Python layer takes any other orthogonal wavelet as its coefficients), padding modes other than reflect / wrap / symmetric / edge,
  * the median down-sampling.  The lightsheet correction of process_img :1333-1348 is mi_lightsheet.h; the Python layer runs it between two
- * plans of this header.
+ * plans of this header, and so it does with the resize to new_size of batch_filter (:1356-1359), which is mi_tile_resize.h;
+ * process_img(new_size=...) itself stays refused.
  *
  * Bleach correction (bleach_frequency > 0), on the float32 log-domain image L (the stripe filter's cropped result, or log1p(tile)
  * when sigma == (0, 0)), just before expm1:
