@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
-"""Stitching steps 2-4 ("pairwise displacement computation", projection, thresholding) entry point.
+"""Stitching steps 1-6 entry point: import, pairwise displacement computation, projection, thresholding, placement, merge.
 
-The reference's process_images.py builds ``mpiexec ... Parastitcher.py -2 --sD=.. --subvoldim=.. --threshold=0.65
+Step 1 is a drop-in for ``terastitcher -1`` (the reference's process_images.py:460-476 builds exactly this line):
+
+    python process_images.py -1 --ref1=H --ref2=V --ref3=D --vxl1=0.8 --vxl2=0.8 --vxl3=2 --sparse_data
+                                --volin=TILES_DIR --projout=xml_import_step_1.xml --noprogressbar
+
+``TILES_DIR`` is the two-level folder of 2-D TIFF series ``<first>/<first>_<second>/<first>_<second>_<z>.tif`` (or ``<z>.tif``),
+coordinates in 0.1 um; ``--ref1..3`` name the axes of the first, second and third coordinate (V, H, D, -V, -H, or 1, 2, 3, -1,
+-2; the 40x objective uses ``--ref1=V --ref2=H``).  The project is built from directory names, file names and one TIFF header per
+stack (``ipp_amd.tsproject.Project.from_folder``: StackedVolume::init, Stack::init, applyReferenceSystem) and written in the
+reference's format.  ``mdata.bin`` is neither written nor read; other ``--volin_plugin`` / ``--imin_plugin`` than
+``TiledXY|2Dseries`` / ``tiff2D`` are refused.
+
+Steps 2-4.  The reference's process_images.py builds ``mpiexec ... Parastitcher.py -2 --sD=.. --subvoldim=.. --threshold=0.65
 --projin=.. --projout=..`` and toggles the GPU kernels with ``USECUDA_X_NCC`` (process_images.py:542-571,1552); the
 work behind that command is StackStitcher::computeDisplacements -> PDAlgoMIPNCC::execute -> norm_cross_corr_mips.
 This entry point keeps the step-2 flags and runs that work in-process on the MI355X library:
@@ -16,8 +28,8 @@ the shape of DisplacementMIPNCC::getXML (DisplacementMIPNCC.cpp:367-400).
     python process_images.py -3 --input TILES_DIR [--projin xml_displcomp.xml --projout xml_displproj.xml]
     python process_images.py -4 --input TILES_DIR [--threshold 0.65 --projin xml_displproj.xml --projout xml_displthres.xml]
 
-With a TeraStitcher project file the three steps are drop-ins for ``terastitcher -2 / -3 / -4`` between the reference's
-import (``-1``) and placement (``-5``) steps (process_images.py:461-576 builds exactly these command lines):
+With a TeraStitcher project file (step 1's, or one ``terastitcher -1`` wrote) the three steps are drop-ins for
+``terastitcher -2 / -3 / -4`` (process_images.py:461-576 builds exactly these command lines):
 
     python process_images.py -2 --projin xml_import_step_1.xml --projout xml_import_step_2.xml [--sD 10 --subvoldim 100]
     python process_images.py -3 --projin xml_import_step_2.xml --projout xml_import_step_3.xml
@@ -38,8 +50,8 @@ Steps 5 and 6 are drop-ins for ``terastitcher -5 / -6`` (project files only):
                                 [--slicewidth W --sliceheight H --D0 z0 --D1 z1 --algorithm SINBLEND|NOBLEND] [--resolutions 0]
 
 Step 5 is the MST placement (TPAlgoMST::execute, host); step 6 merges the placed stacks on the device (include/mi_stitch.h) and
-writes the reference's RES(VxHxD)/V/V_H/V_H_D.tif tree at resolution 0.  Step 1 (import) and the interactive pipeline around
-the steps stay with the reference's tools.
+writes the reference's RES(VxHxD)/V/V_H/V_H_D.tif tree at resolution 0.  The interactive pipeline around the steps stays with
+the reference's tools.
 With ``torchrun`` the pairs of a layer are dealt round-robin to the ranks (no collective; the per-rank XML fragments
 are merged by rank 0, like Parastitcher's mergedisplacements); under step 6 each rank writes a contiguous range of output slices.
 """
@@ -82,6 +94,16 @@ def build_parser():
     p.add_argument("--D0", type=int, default=-1, help="step 6: first output slice")
     p.add_argument("--D1", type=int, default=-1, help="step 6: last output slice (included, as terastitcher's --D1)")
     p.add_argument("--resolutions", default="0", help="step 6: output resolutions (only 0 is built)")
+    p.add_argument("-1", "--import", dest="step1", action="store_true", help="step 1: import a tile folder into a project (host)")
+    p.add_argument("--volin", default=None, help="step 1: folder of the tiles, <first coordinate>/<first>_<second>/<slices>.tif")
+    for k, what in ((1, "first"), (2, "second"), (3, "third")):
+        p.add_argument(f"--ref{k}", default=None, help=f"step 1: {what} axis of the folder's reference system: V, H, D, -V, -H "
+                                                        "(or Y, X, Z; or 1, 2, 3, -1, -2)")
+        p.add_argument(f"--vxl{k}", type=float, default=0.0, help=f"step 1: voxel size along the {what} axis (um)")
+    p.add_argument("--sparse_data", action="store_true", help="step 1: stacks may miss slices or be empty")
+    p.add_argument("--volin_plugin", default="TiledXY|2Dseries", help="step 1: input volume format (TiledXY|2Dseries only)")
+    p.add_argument("--imin_plugin", default="tiff2D", help="step 1: image reader (tiff2D only)")
+    p.add_argument("--noprogressbar", action="store_true", help="accepted for terastitcher's command lines")
     return p
 
 
@@ -254,6 +276,26 @@ def project_steps(args):
     return 0
 
 
+def step1_import(args):
+    """terastitcher -1: the project file of a tile folder (tsproject.Project.from_folder; names and TIFF headers only)."""
+    from ipp_amd import tsproject
+    if args.volin_plugin != tsproject.FORMAT_ID:
+        raise SystemExit(f"-1: --volin_plugin \"{args.volin_plugin}\" is not built: {tsproject.FORMAT_ID} only")
+    if args.imin_plugin != "tiff2D":
+        raise SystemExit(f"-1: --imin_plugin \"{args.imin_plugin}\" is not built: tiff2D only")
+    refs, vxls = (args.ref1, args.ref2, args.ref3), (args.vxl1, args.vxl2, args.vxl3)
+    if args.volin is None or args.projout is None or None in refs or 0.0 in vxls:
+        raise SystemExit("-1 needs --volin, --projout, --ref1 --ref2 --ref3 and --vxl1 --vxl2 --vxl3")
+    try:
+        proj = tsproject.Project.from_folder(args.volin, [tsproject.str2axis(r) for r in refs], vxls, args.sparse_data,
+                                             args.imin_plugin)
+    except ValueError as e:
+        raise SystemExit(f"-1: {e}")
+    proj.save(args.projout)
+    print(f"wrote {args.projout} ({proj.N_ROWS} x {proj.N_COLS} stacks of {proj.N_SLICES} slices)")
+    return 0
+
+
 def step5_place(args):
     """terastitcher -5: ABS_V/H/D from the thresholded displacements (tsproject.Project.computeTilesPlacement)."""
     from ipp_amd import tsproject
@@ -318,6 +360,8 @@ def step6_merge(args):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.step1:
+        return step1_import(args)
     if args.step5:
         return step5_place(args)
     if args.step6:

@@ -3,6 +3,8 @@ steps 2-4: the volume descriptor the reference's ``terasti
 reads, with the per-stack NORTH / EAST / SOUTH / WEST displacement lists in between.  Host-side bookkeeping; the pairwise
 computation itself is ``crossmips.compute_displacements`` (GPU).
 
+  Project.from_folder            step 1, the import: StackedVolume::init / applyReferenceSystem (vmStackedVolume.cpp:277-560),
+                                 Stack::init / compute_z_ranges (vmStack.cpp:165-250, 792-846); names and TIFF headers only
   Project.load / save            StackedVolume::initFromXML / saveXML (vmStackedVolume.cpp:661-746, 748-870), Stack::getXML /
                                  loadXML (vmStack.cpp:356-399, 401-548); format id "TiledXY|2Dseries" (vmStackedVolume.cpp:96)
   insertDisplacement             VirtualVolume::insertDisplacement (vmVirtualVolume.cpp:280-314)
@@ -70,6 +72,10 @@ class Stack:
     EAST: list = field(default_factory=list)
     SOUTH: list = field(default_factory=list)
     WEST: list = field(default_factory=list)
+    HEIGHT: int = -1                                 # known after an import (from_folder) only, like FILENAMES:
+    WIDTH: int = -1                                  # the slice names aligned to the volume's z coordinates, None = missing
+    DEPTH: int = -1
+    FILENAMES: list = None
 
     def isComplete(self, z0: int, z1: int) -> bool:
         """vmVirtualStack: every slice of [z0, z1] (inclusive) is present."""
@@ -119,6 +125,159 @@ class Stack:
         return s
 
 
+_AXIS_NAMES = {1: ("vertical", "1", "v", "V", "Y", "y"), 2: ("horizontal", "2", "h", "H", "X", "x"), 3: ("depth", "3", "d", "D", "Z", "z")}
+
+
+def str2axis(text: str) -> int:
+    """vm::str2axis (volumemanager.config.h:147-163): +-1 = V, +-2 = H, +-3 = D, 0 = invalid."""
+    for code, names in _AXIS_NAMES.items():
+        if text in names:
+            return code
+        if text == "inv_" + names[0] or (text[:1] == "-" and text[1:] in names[1:]):
+            return -code
+    return 0
+
+
+def name2coordZ(filename: str) -> str:
+    """VirtualVolume::name2coordZ (vmVirtualVolume.cpp:197-209): the z coordinate string of ``[0-9]+_[0-9]+_[0-9]+.*`` or
+    ``[0-9]+.*`` -- the last '_' token without its extension."""
+    last = filename.split("_")[-1]
+    dot = last.rfind(".")
+    return last if dot < 0 else last[:dot]
+
+
+def _scan_int(token: str):
+    """sscanf(token, "%d"): the leading integer, or None."""
+    m = re.match(r"\s*([+-]?\d+)", token)
+    return int(m.group(1)) if m else None
+
+
+def _extract_coordinates(stk: Stack, with_z=False):
+    """VirtualVolume::extractCoordinates (vmVirtualVolume.cpp:212-277) at z = 0: the first two numbers among the '/' and '_'
+    tokens of DIR_NAME after the first one (in 0.1 um), and the number in the last '_' token of the first slice's name."""
+    found = []
+    for tok in [t for t in re.split(r"[/_]", stk.DIR_NAME) if t][1:]:
+        if len(found) == 2:
+            break
+        v = _scan_int(tok)
+        if v is not None:
+            found.append(v)
+    if len(found) < 2:
+        raise ValueError(f"in VirtualVolume::extractCoordinates(directory_name=\"{stk.DIR_NAME}\"): format 000000_000000 or "
+                         "X_000000_X_000000 not found")
+    if not with_z:
+        return tuple(found)
+    if not stk.isComplete(0, 0):
+        raise ValueError(f"in VirtualVolume::extractCoordinates(directory_name=\"{stk.DIR_NAME}\"): no slice found at z=0")
+    name = stk.FILENAMES[0]
+    tokens = [t for t in name.split("_") if t]
+    stem = [t for t in tokens[-1].split(".") if t] if tokens else []
+    z = _scan_int(stem[0]) if stem else None
+    if z is None:
+        raise ValueError(f"in VirtualVolume::extractCoordinates(...): unable to extract Z position from filename {name}")
+    return found[0], found[1], z
+
+
+def _tiff_header(path):
+    """tiff2D::readMetadata (tiff2D.cpp:98-187): WIDTH, HEIGHT, N_BYTESxCHAN, N_CHANS from the TIFF header; no pixel is read."""
+    from PIL import Image
+    try:
+        with Image.open(path) as im:
+            tags = getattr(im, "tag_v2", None)
+            if tags is None or 258 not in tags:
+                raise OSError("no TIFF tags")
+            bps = tags[258]
+            bps = bps[0] if isinstance(bps, tuple) else bps
+            pages = getattr(im, "n_frames", 1)
+            width, height, spp = im.width, im.height, int(tags.get(277, 1))
+    except (OSError, SyntaxError, ValueError) as e:
+        raise ValueError(f"in tiff2D::readMetadata(): unable to open image \"{path}\". Possible unsupported format or it isn't "
+                         "an image.\nSupported format is 2DTIFF") from e
+    if pages > 1:
+        raise ValueError(f"in tiff2D::readMetadata(): image \"{path}\" has more than one page.\nSupported format is 2DTIFF")
+    return width, height, int(bps) // 8, spp
+
+
+def _list_dir(path, error):
+    try:
+        return sorted(os.listdir(os.fsencode(path)))             # byte strings, like std::list<std::string>::sort
+    except OSError as e:
+        raise ValueError(error) from e
+
+
+def _scan_folder(stacks_dir: str, sparse_data: bool):
+    """StackedVolume::init (vmStackedVolume.cpp:277-420) with Stack::init (vmStack.cpp:165-250): the grid of Stack.
+    Rows are the first-level entries, columns the second-level ones, both without '.' or ' ' in their names; the slices are
+    the third-level names with a '.'.  Under ``sparse_data`` every stack is aligned to the volume's set of z coordinates."""
+    def is_dir_entry(name):
+        return b"." not in name and b" " not in name
+    lev1 = [n for n in _list_dir(stacks_dir, f"in StackedVolume::init(...): Unable to open directory \"{stacks_dir}\"")
+            if is_dir_entry(n)]
+    if not lev1:
+        raise ValueError("in StackedVolume::init(...): Unable to find stacks in the given directory")
+    grid, n_cols = [], 0
+    for i, d1 in enumerate(lev1):
+        lev2 = [n for n in _list_dir(os.path.join(os.fsencode(stacks_dir), d1),
+                                     "in StackedVolume::init(...): A problem occurred during scanning of subdirectories")
+                if is_dir_entry(n)]
+        row = []
+        for j, d2 in enumerate(lev2):
+            s = Stack(i, j, os.fsdecode(d1) + "/" + os.fsdecode(d2), N_CHANS=0, N_BYTESxCHAN=0)
+            folder = f"{stacks_dir}/{s.DIR_NAME}"
+            names = _list_dir(folder, f"in Stack::init(): can't open directory \"{folder}\"")
+            s.FILENAMES = [os.fsdecode(n) for n in names if b"." in n and n not in (b".", b"..", b"Thumbs.db")]
+            s.DEPTH = len(s.FILENAMES)
+            if s.DEPTH:
+                s.WIDTH, s.HEIGHT, s.N_BYTESxCHAN, s.N_CHANS = _tiff_header(f"{folder}/{s.FILENAMES[0]}")
+                s.z_ranges = [(0, s.DEPTH)]
+            elif not sparse_data:
+                raise ValueError(f"in Stack[{s.DIR_NAME}]::init(): stack is empty. If that was your intent, please use the "
+                                 "'--sparse_data' option")
+            row.append(s)
+        if n_cols == 0:
+            n_cols = len(row)
+        elif len(row) != n_cols:
+            raise ValueError("in StackedVolume::init(...): Number of second-level directories is not the same for all "
+                             "first-level directories!")
+        grid.append(row)
+    if n_cols == 0:
+        raise ValueError("in StackedVolume::init(...): Unable to find stacks in the given directory")
+    if sparse_data:
+        # N_SLICES: the distinct z coordinate strings of the whole volume, in string order (std::set<std::string>)
+        z_coords = sorted({name2coordZ(f).encode() for row in grid for s in row for f in s.FILENAMES})
+        n_slices = len(z_coords)
+        if n_slices == 0:
+            raise ValueError("in StackedVolume::init(...): Unable to find image files in the given directory")
+        for row in grid:
+            for s in row:                                        # Stack::compute_z_ranges (vmStack.cpp:792-846)
+                aligned, k = [], 0
+                for z in z_coords:
+                    if k < s.DEPTH and z == name2coordZ(s.FILENAMES[k]).encode():
+                        aligned.append(s.FILENAMES[k])
+                        k += 1
+                    else:
+                        aligned.append(None)
+                s.FILENAMES, s.DEPTH, s.z_ranges = aligned, n_slices, []
+                start = None
+                for k, f in enumerate(aligned + [None]):
+                    if f is not None and start is None:
+                        start = k
+                    elif f is None and start is not None:
+                        s.z_ranges.append((start, k))
+                        start = None
+    # normalize_stacks_attributes (:1773-1799): one height and one width; empty stacks take them
+    full = [s for row in grid for s in row if s.z_ranges]
+    heights, widths = {s.HEIGHT for s in full}, {s.WIDTH for s in full}
+    if len(heights) != 1 or len(widths) != 1:
+        raise ValueError("in StackedVolume::normalize_stacks_attributes(...): Stacks have unequal X,Y dimensions. This feature "
+                         "is not supported yet.")
+    for row in grid:
+        for s in row:
+            if not s.z_ranges:
+                s.HEIGHT, s.WIDTH = next(iter(heights)), next(iter(widths))
+    return grid
+
+
 class Project:
     """The stitching project: volume descriptor + STACKS[row][col] (vmStackedVolume.h, vmVirtualVolume.h)."""
 
@@ -154,6 +313,77 @@ class Project:
     def getDEFAULT_DISPLACEMENT_V(self): return int(abs(self._fdiv(self.MEC_V, self.VXL_V)))
     def getDEFAULT_DISPLACEMENT_H(self): return int(abs(self._fdiv(self.MEC_H, self.VXL_H)))
     def getDEFAULT_DISPLACEMENT_D(self): return 0
+
+    # ---- import (step 1)
+    @classmethod
+    def from_folder(cls, stacks_dir, ref_sys, vxl, sparse_data=False, input_plugin="tiff2D"):
+        """Step 1: the project of a two-level tile folder, as ``terastitcher -1`` builds it (StackedVolume::StackedVolume ->
+        init -> applyReferenceSystem).  ``ref_sys`` holds the signed axis codes of the three folder / file coordinates (+-1 = V,
+        +-2 = H, 3 = D), ``vxl`` the voxel sizes in the same order.  Only names and the TIFF header of each stack's first slice
+        are read; a ``mdata.bin`` in the folder is neither read nor written."""
+        stacks_dir = str(stacks_dir)
+        ref = tuple(int(v) for v in ref_sys)
+        VXL = [np.float32(v) for v in vxl]
+        if len(ref) != 3 or len(VXL) != 3 or 0 in ref or any(v == 0 for v in VXL):
+            raise ValueError("in StackedVolume::StackedVolume(...): invalid importing parameters")
+        if input_plugin != "tiff2D":
+            raise ValueError(f"in StackedVolume::init(...): input plugin \"{input_plugin}\" is not built: tiff2D only")
+        grid = _scan_folder(stacks_dir, sparse_data)
+        # applyReferenceSystem (vmStackedVolume.cpp:428-560): the voxel sizes take the signs of their axes
+        VXL = [-v if (r < 0) != (v < 0) else v for r, v in zip(ref, VXL)]
+        hvd = abs(ref[0]) == 2 and abs(ref[1]) == 1 and ref[2] == 3
+        if hvd:                                                  # rotate(90) then mirror(2): the grid transposed
+            grid = [list(col) for col in zip(*grid)]
+        elif not (abs(ref[0]) == 1 and abs(ref[1]) == 2 and ref[2] == 3):
+            raise ValueError("in StackedVolume::init(...): the reference system {%d,%d,%d} is not supported." % ref)
+        if -1 in ref:                                            # mirror(1): rows reversed
+            grid = grid[::-1]
+        if -2 in ref:                                            # mirror(2): columns reversed
+            grid = [row[::-1] for row in grid]
+        n_rows, n_cols = len(grid), len(grid[0])
+        first = grid[0][0]
+        if not first.isComplete(0, 0):
+            raise ValueError("in StackedVolume::applyReferenceSystem(): cannot compute origin. Tile (0,0) "
+                             f"[{first.DIR_NAME}] has no slice at z=0")
+        f32 = np.float32
+        c1, c2, c3 = _extract_coordinates(first, with_z=True)
+        VXL_V, VXL_H, VXL_D = (VXL[1], VXL[0], VXL[2]) if hvd else VXL
+        ORG_V, ORG_H, ORG_D = (f32(c) / f32(10000) for c in ((c2, c1, c3) if hvd else (c1, c2, c3)))
+        v_of = (lambda c: c[1]) if hvd else (lambda c: c[0])     # which folder coordinate runs along V / along H
+        h_of = (lambda c: c[0]) if hvd else (lambda c: c[1])
+        if n_rows > 1:
+            MEC_V = f32(v_of(_extract_coordinates(grid[1][0])) - v_of((c1, c2))) / f32(10)
+        else:
+            MEC_V = f32(first.HEIGHT) * VXL_V
+        if n_cols > 1:
+            MEC_H = f32(h_of(_extract_coordinates(grid[0][1])) - h_of((c1, c2))) / f32(10)
+        else:
+            MEC_H = f32(first.WIDTH) * VXL_H
+        n_slices = first.DEPTH                                   # (:489, :529; under sparse_data the volume's z set)
+        if VXL_V < 0:
+            ORG_V = f32(ORG_V - f32(first.HEIGHT - 1) * VXL_V / f32(1000))
+        if VXL_H < 0:
+            ORG_H = f32(ORG_H - f32(first.WIDTH - 1) * VXL_H / f32(1000))
+        p = cls(stacks_dir, n_rows, n_cols, n_slices, (VXL_V, VXL_H, VXL_D), (ORG_V, ORG_H, ORG_D), (MEC_V, MEC_H), ref,
+                input_plugin, f"{stacks_dir}/mdata.bin")
+        p._dims = (first.HEIGHT, first.WIDTH)
+        dV, dH, dD = p.getDEFAULT_DISPLACEMENT_V(), p.getDEFAULT_DISPLACEMENT_H(), p.getDEFAULT_DISPLACEMENT_D()
+        for i in range(n_rows):
+            for j in range(n_cols):
+                s = grid[i][j]
+                s.ROW_INDEX, s.COL_INDEX = i, j
+                s.ABS_V = p.STACKS[i - 1][j].ABS_V + dV if i else 0
+                s.ABS_H = p.STACKS[i][j - 1].ABS_H + dH if j else 0
+                s.ABS_D = dD
+                p.STACKS[i][j] = s
+        if not sparse_data:                                      # StackedVolume::StackedVolume (:134-146)
+            for row in p.STACKS:
+                for s in row:
+                    if s.DEPTH != n_slices:
+                        raise ValueError("in StackedVolume::StackedVolume(): unequal number of slices detected. Stack "
+                                         f"\"{first.DIR_NAME}\" has {first.DEPTH}, stack \"{s.DIR_NAME}\" has {s.DEPTH}. "
+                                         "Please activate the sparse data option if stacks are not complete")
+        return p
 
     # ---- files
     @classmethod
