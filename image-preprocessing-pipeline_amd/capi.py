@@ -233,6 +233,7 @@ SIGNATURES = {
     "mi_pyramid_slab": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _ip, C.POINTER(_vp)]),
     "mi_tiff3d_write_blocks": (_i, [_i, C.POINTER(C.c_char_p), C.POINTER(_vp), C.POINTER(C.c_int64), _ip, _ip, _ip, _i, _i, _i, _i,
                                     _i]),
+    "mi_tiff_deflate_strip_host": (_i, [_vp, C.c_size_t, _i, C.c_size_t, _i, _i, _vp, C.c_size_t, C.POINTER(C.c_size_t), _ip]),
     "mi_tiff_lzw_encode": (_i, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64)]),
     # mi_pystripe.h
     "mi_pystripe_plan_create": (_i, [_i, _i, _i, _i, C.POINTER(PystripeParams), C.POINTER(_vp)]),

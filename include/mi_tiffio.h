@@ -38,11 +38,21 @@ int mi_tiff_write_series(const char* const* paths, int nz, const void* vol, int 
                          int n_threads, int* written);
 
 /* The same files from a volume that lies in DEVICE memory (vol [nz][ny][nx] on device `dev`), deflated there: every strip is one
- * dynamic-Huffman block without string matching (csrc/tiffio.hip: histogram kernel, codes built on the host, encode kernel), the host
- * only frames the streams and writes the files.  Adobe deflate always; readable by any inflater.  Enqueues on `stream` and
- * synchronises it.  No counterpart in the reference (save_bl_tif.cpp compresses on the host's cores). */
+ * dynamic-Huffman block (csrc/tiffio.hip: counting kernels, codes built on the host, encode kernel), the host only frames the streams
+ * and writes the files.  The only string matching is that of runs: a strip is coded either with every byte a literal, or -- when that
+ * is shorter, as on the zero background of a stitched or clipped volume -- with its runs of equal bytes as matches at distance 1
+ * (zlib's Z_RLE; the token rule is in DESIGN.md, "TIFF on the device").  MI_TIFF_DEVICE_RUNS=0 in the environment (read per call)
+ * keeps every strip in the literal form.  Adobe deflate always; readable by any inflater.  Enqueues on `stream` and synchronises
+ * it.  No counterpart in the reference (save_bl_tif.cpp compresses on the host's cores). */
 int mi_tiff_write_series_device(int dev, void* stream, const char* const* paths, int nz, const void* vol, int dtype, int nx, int ny,
                                 int n_threads, int* written);
+
+/* one strip (n bytes, rows of rowb bytes, samples of bps bytes) as the device writer codes it, computed on the host by the same rule:
+ * pred 0 / 1 (horizontal differencing), runs 0 (literal-only) / 1 (the shorter of the two forms); the whole zlib stream goes to out.
+ * *nbytes receives its length (MI_ERR_NOMEM when cap is smaller; n + n / 32 + 4096 always suffices), *used_runs (may be NULL)
+ * whether the run form was taken.  The yardstick of the device path in tests; needs no GPU. */
+int mi_tiff_deflate_strip_host(const unsigned char* bytes, size_t n, int bps, size_t rowb, int pred, int runs, unsigned char* out, size_t cap,
+                               size_t* nbytes, int* used_runs);
 
 /* One RGB file per z slice of vol [nz][ny][nx][3] (host memory), the `RGB` series of align_images.py: classic little-endian TIFF,
  * SamplesPerPixel 3, PhotometricInterpretation 2 (RGB), PlanarConfiguration 1 (chunky), strips, SampleFormat per type.
