@@ -22,7 +22,10 @@ SINBLEND, NOBLEND = 0, 1   # mi_blending (include/mi_stitch.h)
 HALVE_MEAN, HALVE_MAX = 0, 1   # mi_halve_method (include/mi_pyramid.h)
 PS_U8, PS_U16, PS_F32 = 0, 1, 2   # mi_pystripe_dtype (include/mi_pystripe.h)
 PS_PADDING = {"reflect": 0, "wrap": 1, "symmetric": 2, "edge": 3}   # mi_pystripe_padding
-PS_DOWN = {"max": 0, "min": 1, "mean": 2}   # mi_pystripe_down
+PS_DOWN = {"max": 0, "min": 1, "mean": 2, "median": 3}   # mi_pystripe_down
+PS_MEDIAN_MAX_BLOCK = 64  # MI_PS_MEDIAN_MAX_BLOCK
+PS_AUTO_MIN, PS_AUTO_MED, PS_AUTO_MAX = 1, 2, 4   # bits of PystripeParams.bleach_auto (MI_PS_AUTO_*)
+PS_CLIPS_UNIFORM, PS_CLIPS_OK, PS_CLIPS_TOO_FEW, PS_CLIPS_ORDER, PS_CLIPS_NONFINITE = -1, 0, 1, 2, 3   # mi_pystripe_clip_status
 CODES_U8, CODES_U16 = 0, 1   # mi_code_dtype (include/mi_thresholds.h)
 OTSU_OK, OTSU_TOO_FEW_VALUES, OTSU_VALUES_ARE_CLASSES = 0, 1, 2   # mi_otsu_status
 
@@ -67,6 +70,14 @@ class PystripeParams(C.Structure):
                 ("log_output", C.c_int), ("max_batch", C.c_int), ("keep_uniform", C.c_int), ("bleach_frequency", C.c_double),
                 ("bleach_clip_min", C.c_double), ("bleach_clip_med", C.c_double), ("bleach_clip_max", C.c_double),
                 ("bleach_max_method", C.c_int)]
+
+    @property
+    def bleach_auto(self):
+        """PS_AUTO_* bits of the clips that are NaN: those the plan estimates per tile (0 without a bleach_frequency)"""
+        if not self.bleach_frequency:
+            return 0
+        clips = (self.bleach_clip_min, self.bleach_clip_med, self.bleach_clip_max)
+        return sum(bit for bit, v in zip((PS_AUTO_MIN, PS_AUTO_MED, PS_AUTO_MAX), clips) if v != v)
 
 
 PS_MAX_LEVELS = 24  # MI_PS_MAX_LEVELS
@@ -244,6 +255,8 @@ SIGNATURES = {
     "mi_pystripe_derive": (_i, [_i, _i, _i, C.POINTER(PystripeParams), C.POINTER(PystripeInfo)]),
     "mi_pystripe_run": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64]),
     "mi_pystripe_pad_size": (_i, [_i, _i, C.c_double]),
+    "mi_pystripe_plan_set_log_table": (_i, [_vp, _vp, _i]),
+    "mi_pystripe_plan_clips": (_i, [_vp, _vp, _vp, _i]),
     # mi_lightsheet.h
     "mi_lightsheet_derive": (_i, [_i, _i, _i, C.POINTER(LightsheetParams), C.POINTER(LightsheetInfo)]),
     "mi_lightsheet_plan_create": (_i, [_i, _i, _i, _i, C.POINTER(LightsheetParams), C.POINTER(_vp)]),

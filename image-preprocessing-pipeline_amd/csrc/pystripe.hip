@@ -21,6 +21,9 @@
 //             L is log1p on load and never stored); a work-group per row runs sosfiltfilt's forward-backward first-order
 //             recurrence in float64 as a scan of affine maps over the clipped, odd-extended row in LDS and writes F and its row
 //             maximum; a block per tile reduces the maxima; the apply pass hands (L / F) * max F to the same store.
+//   clips     a clip given as NaN: threshold_multiotsu(log1p(tile), 4) per tile before anything else of the run (the "automatic clips" section
+//             below): range and 256-bin histogram of the source read through src_load, the search and edges of thresholds.hip,
+//             a triple and a status per tile in device memory; the row filter takes its clips from there.
 //   wavelets  the kernels named above are db9's (mi_pystripe_plan_create); mi_pystripe_plan_create_wavelet runs their counterparts
 //             for any even tap count up to MI_PS_MAX_TAPS (the *_gen_kernel section): same load, notch, store and bleach route.
 #include <hip/hip_runtime.h>
@@ -33,6 +36,7 @@
 
 #include "mi_internal.h"
 #include "mi_pystripe.h"
+#include "thresholds_dev.h"
 
 namespace mi {
 namespace {
@@ -134,10 +138,12 @@ struct Sink {
     float cast_max;
     int flip, rot;
     const int* varies;      // per tile: 0 = uniform tile -> zeros
+    const int* clip_status; // automatic clips: per tile, > 0 = no usable clips -> zeros, also in the log output; else null
 };
 
 __device__ __forceinline__ void sink_store(const Sink& k, i64 tile, int y, int x, float v) {
     if (k.log_out) {
+        if (k.clip_status && k.clip_status[tile] > 0) v = 0.f;
         static_cast<float*>(k.out)[tile * k.tile_stride + (i64)y * k.nx + x] = v;
         return;
     }
@@ -228,6 +234,62 @@ __global__ void __launch_bounds__(256) pre_kernel(Src s, const float* flat, int 
         }
     const float r = method == MI_PS_DOWN_MAX ? mx : method == MI_PS_DOWN_MIN ? mn : (float)(sum / (double)(by * bx));
     stage[tile * ((i64)ny * nx) + (i64)y * nx + x] = r;
+}
+
+// block_reduce with numpy.median: the by * bx <= N samples of a block (zeros beyond the tile, +inf up to N) are sorted in registers
+// by a bitonic network, every index static; an even count gives the mean of the two middle values, taken in float64.
+template <int N>
+__global__ void __launch_bounds__(256) pre_median_kernel(Src s, const float* flat, int by, int bx, float* stage, int ny, int nx) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const i64 tile = blockIdx.z;
+    if (x >= nx || y >= ny) return;
+    const int cnt = by * bx;
+    float v[N];
+    int dy = 0, dx = 0;
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+        float t = INFINITY;
+        if (e < cnt) {
+            const int yy = y * by + dy, xx = x * bx + dx;
+            t = 0.f;
+            if (yy < s.ny && xx < s.nx) {
+                t = src_load(s, tile, yy, xx);
+                if (flat) t = t / flat[(i64)yy * s.nx + xx];
+            }
+            if (++dx == bx) { dx = 0; ++dy; }
+        }
+        v[e] = t;
+    }
+#pragma unroll
+    for (int k = 2; k <= N; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const bool up = (i & k) == 0;
+                    const float lo = fminf(v[i], v[l]), hi = fmaxf(v[i], v[l]);
+                    v[i] = up ? lo : hi;
+                    v[l] = up ? hi : lo;
+                }
+            }
+        }
+    }
+    const int k0 = (cnt - 1) / 2, k1 = cnt / 2;
+    float a = 0.f, b = 0.f;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        if (i == k0) a = v[i];
+        if (i == k1) b = v[i];
+    }
+    stage[tile * ((i64)ny * nx) + (i64)y * nx + x] = (float)(((double)a + (double)b) * 0.5);
+}
+
+template <int N>
+int launch_pre_median(hipStream_t st, dim3 grid, const Src& s, const float* flat, int by, int bx, float* stage, int ny, int nx) {
+    hipLaunchKernelGGL(pre_median_kernel<N>, grid, dim3(256), 0, st, s, flat, by, bx, stage, ny, nx);
+    return launch_check("pre_median_kernel");
 }
 
 // no stripe filter: every sample straight to the sink
@@ -656,6 +718,7 @@ static_assert(kBleachSeg - 2 * kBleachExt == MI_PS_BLEACH_LDS_ROW, "MI_PS_BLEACH
 struct Bleach {
     double b, a;              // y = b u + z;  z' = b u + a y
     float lo, med, hi;        // G = clip(L == 0 ? med : L, lo, hi)
+    const float* clips;       // automatic clips: [tile][3] = lo, med, hi in device memory, instead of the three above; else null
 };
 
 __device__ __forceinline__ double bleach_sample(const Src& s, const Bleach& q, i64 tile, int line, int j) {
@@ -730,6 +793,10 @@ __global__ void __launch_bounds__(kBleachMaxThreads) bleach_filter_kernel(Src s,
     double2* tot = reinterpret_cast<double2*>(u + cap + (cap & 1));
     const int line = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
     const i64 tile = blockIdx.y;
+    if (q.clips) {
+        const float* c = q.clips + 3 * tile;
+        q.lo = c[0]; q.med = c[1]; q.hi = c[2];
+    }
     float* f = F + tile * f_tile_stride + (i64)line * f_row;
     float mx = -INFINITY;
     if (len <= seg) {
@@ -846,6 +913,107 @@ __global__ void __launch_bounds__(256) bleach_apply_kernel(Src s, const float* F
     sink_store(k, tile, y, x, v * M[tile]);
 }
 
+// ---- automatic clips (filter_streaks :1066-1077: threshold_multiotsu(log1p(tile), classes=4)) --------------------------------------
+// The value of a sample of the log image: for an integer-kind tile table[code] (numpy's float32 log1p of the code, so that the
+// counts are numpy.histogram's exactly; the staged float of a max / min down-sample is a whole code), else log1pf on load (s.logp).
+
+__device__ __forceinline__ float auto_value(const Src& s, const float* table, int ncodes, i64 tile, int y, int x) {
+    const float v = src_load(s, tile, y, x);
+    return table ? table[min(max((int)v, 0), ncodes - 1)] : v;
+}
+
+// finite range per tile as keys (thresholds.hip's minmax_kernel on this source); rows over the work-groups of grid.x
+__global__ void __launch_bounds__(256) auto_range_kernel(Src s, const float* table, int ncodes, unsigned* keys, int* nonfinite) {
+    const i64 tile = blockIdx.y;
+    float lo = INFINITY, hi = -INFINITY;
+    int bad = 0;
+    for (int y = blockIdx.x; y < s.ny; y += gridDim.x)
+        for (int x = threadIdx.x; x < s.nx; x += 256) {
+            const float v = auto_value(s, table, ncodes, tile, y, x);
+            if (fabsf(v) < INFINITY) {
+                lo = fminf(lo, v);
+                hi = fmaxf(hi, v);
+            } else {
+                bad = 1;
+            }
+        }
+    for (int d = 32; d >= 1; d >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, d));
+        hi = fmaxf(hi, __shfl_xor(hi, d));
+        bad |= __shfl_xor(bad, d);
+    }
+    // one pair of atomics per work-group: every group of a tile lands on the same two addresses, and they run one after the other
+    __shared__ float wlo[4], whi[4];
+    __shared__ int wbad[4];
+    if ((threadIdx.x & 63u) == 0) {
+        wlo[threadIdx.x >> 6] = lo;
+        whi[threadIdx.x >> 6] = hi;
+        wbad[threadIdx.x >> 6] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) {
+            lo = fminf(lo, wlo[w]);
+            hi = fmaxf(hi, whi[w]);
+            bad |= wbad[w];
+        }
+        if (lo <= hi) {
+            atomicMin(&keys[2 * tile], histdev::float_key(lo));
+            atomicMax(&keys[2 * tile + 1], histdev::float_key(hi));
+        }
+        if (bad) atomicOr(&nonfinite[tile], 1);
+    }
+}
+
+// numpy.histogram(., 256) per tile (thresholds.hip's hist256_kernel on this source)
+__global__ void __launch_bounds__(256) auto_hist_kernel(Src s, const float* table, int ncodes, const float* edges, const int* nonfinite,
+                                                        unsigned long long* counts) {
+    __shared__ float e[MI_HIST_BINS + 1];
+    __shared__ unsigned h[4][MI_HIST_BINS];
+    const i64 tile = blockIdx.y;
+    const int t = threadIdx.x;
+    if (nonfinite[tile]) return;   // the whole work-group
+    e[t] = edges[tile * (MI_HIST_BINS + 1) + t];
+    if (t == 0) e[MI_HIST_BINS] = edges[tile * (MI_HIST_BINS + 1) + MI_HIST_BINS];
+    for (int w = 0; w < 4; ++w) h[w][t] = 0;
+    __syncthreads();
+    const float e0 = e[0];
+    const float scale = 256.0f / (e[MI_HIST_BINS] - e0);
+    unsigned* mine = h[t >> 6];
+    for (int y = blockIdx.x; y < s.ny; y += gridDim.x)
+        for (int x = t; x < s.nx; x += 256) histdev::wave_count(mine, histdev::hist_bin(e, e0, scale, auto_value(s, table, ncodes, tile, y, x)));
+    __syncthreads();
+    unsigned sum = 0;
+    for (int w = 0; w < 4; ++w) sum += h[w][t];
+    if (sum) atomicAdd(&counts[tile * MI_HIST_BINS + t], (unsigned long long)sum);
+}
+
+// The triple and the status of every tile: given clips keep their slot, an estimated one is the float32 centre of the bin the search
+// named; min is raised to log1p(1); the asserts of correct_bleaching :524-528 on the result.  A tile without usable clips is zeroed
+// through `varies`; its estimated slots hold NaN unless the order check failed (the triple is then what the caller reports).
+__global__ void __launch_bounds__(64) auto_clips_kernel(int cnt, int bits, float gmin, float gmed, float gmax, double floor_lo, const float* edges,
+                                                        const int* indices, const int* otsu_status, const int* nonfinite, int uniform_rule,
+                                                        int* varies, float* clips, int* status) {
+    const int tile = blockIdx.x * 64 + threadIdx.x;
+    if (tile >= cnt) return;
+    float c[3] = {gmin, gmed, gmax};
+    int st = MI_PS_CLIPS_OK;
+    if (uniform_rule && !varies[tile]) st = MI_PS_CLIPS_UNIFORM;
+    else if (nonfinite[tile]) st = MI_PS_CLIPS_NONFINITE;
+    else if (otsu_status[tile] == MI_OTSU_TOO_FEW_VALUES) st = MI_PS_CLIPS_TOO_FEW;
+    const float* e = edges + (i64)tile * (MI_HIST_BINS + 1);
+    for (int k = 0; k < 3; ++k)
+        if ((bits >> k) & 1) {
+            const int i = min(max(indices[tile * (MI_OTSU_MAX_CLASSES - 1) + k], 0), MI_HIST_BINS - 1);
+            c[k] = st == MI_PS_CLIPS_OK ? (e[i] + e[i + 1]) / 2.0f : NAN;
+        }
+    if (st == MI_PS_CLIPS_OK && !(c[0] >= 0.f && c[1] > c[0] && c[2] > c[0] && c[2] > c[1])) st = MI_PS_CLIPS_ORDER;
+    if (st == MI_PS_CLIPS_OK) c[0] = (float)fmax((double)c[0], floor_lo);
+    if (st > 0) varies[tile] = 0;
+    clips[3 * tile] = c[0]; clips[3 * tile + 1] = c[1]; clips[3 * tile + 2] = c[2];
+    status[tile] = st;
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 
 int notch_rise_point(double sigma, double rise) {   // :670
@@ -893,7 +1061,15 @@ struct Plan {
     std::vector<NotchTab> tabs;   // [pass][level 1..L][axis 0: cH along -1, 1: cV along -2]
     DevBuf tw_buf, w_buf, scratch, varies;
     i64 cap = 0;
+    // automatic clips: the work space of the estimate for `cap` tiles; the triples and the status of every tile of the last run
+    // (clips_cap tiles); the log1p table of integer tiles
+    DevBuf auto_buf, clips_buf, status_buf, table_buf;
+    i64 clips_cap = 0, last_count = 0;
+    int ncodes = 0;
+    int au = 0;               // MI_PS_AUTO_* of the clips that are NaN
 };
+
+constexpr size_t kAutoBytesPerTile = MI_HIST_BINS * 8 + 8 + (MI_HIST_BINS + 1) * 4 + 2 * 4 + (MI_OTSU_MAX_CLASSES - 1) * 4 + 3 * 4;
 
 // sizes, modes and the scratch layout: everything that needs no device
 int derive(int ny_in, int nx_in, int in_dtype, const mi_pystripe_params& q, Plan& P) {
@@ -904,7 +1080,7 @@ int derive(int ny_in, int nx_in, int in_dtype, const mi_pystripe_params& q, Plan
     P.filter = q.sigma1 > 0 || q.sigma2 > 0;
     MI_REQUIRE(!P.filter || (q.sigma1 > 0 && q.sigma2 > 0), "np_notch: sigma must be positive (sigma = (%g, %g))", q.sigma1, q.sigma2);
     MI_REQUIRE(q.padding_mode >= MI_PS_REFLECT && q.padding_mode <= MI_PS_EDGE, "mi_pystripe: padding_mode %d", q.padding_mode);
-    MI_REQUIRE(q.down_method >= MI_PS_DOWN_MAX && q.down_method <= MI_PS_DOWN_MEAN, "mi_pystripe: down_method %d", q.down_method);
+    MI_REQUIRE(q.down_method >= MI_PS_DOWN_MAX && q.down_method <= MI_PS_DOWN_MEDIAN, "mi_pystripe: down_method %d", q.down_method);
     MI_REQUIRE(q.down_y >= 0 && q.down_x >= 0 && (q.down_y > 0) == (q.down_x > 0), "mi_pystripe: down_sample (%d, %d)", q.down_y, q.down_x);
     MI_REQUIRE(q.rotate == 0 || q.rotate == 90 || q.rotate == 180 || q.rotate == 270, "mi_pystripe: rotate %d (0, 90, 180, 270)", q.rotate);
     MI_REQUIRE(q.level >= 0 && q.level <= MI_PS_MAX_LEVELS, "mi_pystripe: level %d", q.level);
@@ -915,21 +1091,31 @@ int derive(int ny_in, int nx_in, int in_dtype, const mi_pystripe_params& q, Plan
     mi_pystripe_info& I = P.info;
     std::memset(&I, 0, sizeof I);
     const bool down = q.down_y > 0;
+    if (down && q.down_method == MI_PS_DOWN_MEDIAN && (i64)q.down_y * q.down_x > MI_PS_MEDIAN_MAX_BLOCK)
+        return fail(MI_ERR_UNSUPPORTED, "mi_pystripe: median down_sample over blocks of %d x %d samples (at most %d samples per block)", q.down_y,
+                    q.down_x, MI_PS_MEDIAN_MAX_BLOCK);
     P.pre = down || q.use_flat;
     I.ny = down ? (ny_in + q.down_y - 1) / q.down_y : ny_in;
     I.nx = down ? (nx_in + q.down_x - 1) / q.down_x : nx_in;
-    I.integer_kind = in_dtype != MI_PS_F32 && !q.use_flat && !(down && q.down_method == MI_PS_DOWN_MEAN);
+    I.integer_kind = in_dtype != MI_PS_F32 && !q.use_flat && !(down && (q.down_method == MI_PS_DOWN_MEAN || q.down_method == MI_PS_DOWN_MEDIAN));
     I.max_batch = q.max_batch > 0 ? q.max_batch : 16;
     // grid limits: rows go to gridDim.y, tiles (twice, in the column synthesis) to gridDim.z
     MI_REQUIRE(I.max_batch <= 16384, "mi_pystripe: max_batch %d (at most 16384 tiles per launch)", I.max_batch);
     P.bleach = q.bleach_frequency != 0;
+    // a clip given as NaN is estimated per tile (without a bleach_frequency the three values are not looked at)
+    const int au = !P.bleach ? 0 : (std::isnan(q.bleach_clip_min) ? MI_PS_AUTO_MIN : 0) | (std::isnan(q.bleach_clip_med) ? MI_PS_AUTO_MED : 0) |
+                                       (std::isnan(q.bleach_clip_max) ? MI_PS_AUTO_MAX : 0);
+    P.au = au;
     if (P.bleach) {
         MI_REQUIRE(q.bleach_frequency > 0 && q.bleach_frequency < 1, "mi_pystripe: bleach_frequency %g is not in (0, 1)", q.bleach_frequency);
-        MI_REQUIRE(q.bleach_clip_min >= 0, "mi_pystripe: bleach_clip_min %g is negative", q.bleach_clip_min);
-        MI_REQUIRE(q.bleach_clip_med > q.bleach_clip_min, "mi_pystripe: bleach_clip_med %g is not above bleach_clip_min %g", q.bleach_clip_med,
-                   q.bleach_clip_min);
-        MI_REQUIRE(q.bleach_clip_max > q.bleach_clip_med, "mi_pystripe: bleach_clip_max %g is not above bleach_clip_med %g", q.bleach_clip_max,
-                   q.bleach_clip_med);
+        // the checks between given clips; an estimated one is checked on the device, tile by tile
+        MI_REQUIRE((au & MI_PS_AUTO_MIN) || q.bleach_clip_min >= 0, "mi_pystripe: bleach_clip_min %g is negative", q.bleach_clip_min);
+        MI_REQUIRE((au & (MI_PS_AUTO_MIN | MI_PS_AUTO_MED)) || q.bleach_clip_med > q.bleach_clip_min,
+                   "mi_pystripe: bleach_clip_med %g is not above bleach_clip_min %g", q.bleach_clip_med, q.bleach_clip_min);
+        MI_REQUIRE((au & (MI_PS_AUTO_MED | MI_PS_AUTO_MAX)) || q.bleach_clip_max > q.bleach_clip_med,
+                   "mi_pystripe: bleach_clip_max %g is not above bleach_clip_med %g", q.bleach_clip_max, q.bleach_clip_med);
+        MI_REQUIRE((au & (MI_PS_AUTO_MIN | MI_PS_AUTO_MAX)) || q.bleach_clip_max > q.bleach_clip_min,
+                   "mi_pystripe: bleach_clip_max %g is not above bleach_clip_min %g", q.bleach_clip_max, q.bleach_clip_min);
         // sosfiltfilt's padlen: a filtered line has more than 6 samples
         MI_REQUIRE(I.nx > kBleachExt, "mi_pystripe: bleach correction filters rows of nx = %d samples (after down_sample); at least 7", I.nx);
         MI_REQUIRE(!q.bleach_max_method || I.ny > kBleachExt,
@@ -940,6 +1126,8 @@ int derive(int ny_in, int nx_in, int in_dtype, const mi_pystripe_params& q, Plan
         P.bq.lo = (float)std::max(q.bleach_clip_min, std::log1p(1.0));
         P.bq.med = (float)q.bleach_clip_med;
         P.bq.hi = (float)q.bleach_clip_max;
+        P.bq.clips = nullptr;
+        P.ncodes = au && I.integer_kind ? (in_dtype == MI_PS_U8 ? 256 : 65536) : 0;
     }
     if (q.log_output) {
         MI_REQUIRE(P.filter || P.bleach, "mi_pystripe: log_output needs a stripe filter (sigma > 0) or the bleach correction");
@@ -1164,12 +1352,58 @@ int upload_filter_table(Plan& P, const double* rec_lo) {
     return MI_OK;
 }
 
+// the log1p table of an integer tile's automatic clips: the caller's, or libm's log1pf of every code
+int upload_log_table(Plan& P, const float* table) {
+    if (!P.ncodes) return MI_OK;
+    std::vector<float> own;
+    if (!table) {
+        own.resize((size_t)P.ncodes);
+        for (int c = 0; c < P.ncodes; ++c) own[(size_t)c] = log1pf((float)c);
+        table = own.data();
+    }
+    if (!P.table_buf.p) MI_TRY(P.table_buf.alloc(sizeof(float) * (size_t)P.ncodes));
+    MI_HIP(hipMemcpy(P.table_buf.p, table, sizeof(float) * (size_t)P.ncodes, hipMemcpyHostToDevice));
+    return MI_OK;
+}
+
 int check_taps(const char* who, int taps) {
     MI_REQUIRE(taps >= 2 && taps <= MI_PS_MAX_TAPS && taps % 2 == 0, "%s: wavelet of %d taps (an even number, 2 .. %d)", who, taps, MI_PS_MAX_TAPS);
     return MI_OK;
 }
 
-int run_chunk(Plan& P, hipStream_t st, const void* in, const float* flat, void* out, int cnt) {
+// The clips of the cnt tiles behind `src` (the tile after flat and down_sample, not yet in the log domain) into clips[cnt][3] and
+// status[cnt]: range, edges, histogram, search, triple.  Everything stays on the stream.
+int run_auto_clips(Plan& P, hipStream_t st, Src src, int cnt, int* varies, float* clips, int* status) {
+    const mi_pystripe_info& I = P.info;
+    const mi_pystripe_params& q = P.prm;
+    char* base = P.auto_buf.as<char>();
+    const size_t cap = (size_t)P.cap;
+    unsigned long long* counts = reinterpret_cast<unsigned long long*>(base);
+    unsigned long long* work = counts + MI_HIST_BINS * cap;
+    float* edges = reinterpret_cast<float*>(work + cap);
+    unsigned* keys = reinterpret_cast<unsigned*>(edges + (MI_HIST_BINS + 1) * cap);
+    int* indices = reinterpret_cast<int*>(keys + 2 * cap);
+    int* nonfinite = indices + (MI_OTSU_MAX_CLASSES - 1) * cap;
+    int* nvalues = nonfinite + cap;
+    int* otsu_status = nvalues + cap;
+    const float* table = nullptr;
+    if (I.integer_kind) table = P.table_buf.as<float>();
+    else src.logp = 1;
+    MI_TRY(hist_init_launch(st, keys, nonfinite, counts, cnt));
+    const dim3 grid((unsigned)std::min(I.ny, 256), cnt);   // rows over the groups of a tile: few groups, few same-address atomics at the end
+    hipLaunchKernelGGL(auto_range_kernel, grid, dim3(256), 0, st, src, table, P.ncodes, keys, nonfinite);
+    MI_TRY(launch_check("auto_range_kernel"));
+    MI_TRY(hist_edges_launch(st, keys, edges, cnt));
+    hipLaunchKernelGGL(auto_hist_kernel, grid, dim3(256), 0, st, src, table, P.ncodes, edges, nonfinite, counts);
+    MI_TRY(launch_check("auto_hist_kernel"));
+    MI_TRY(multiotsu_launch(st, counts, cnt, MI_OTSU_MAX_CLASSES, indices, nvalues, otsu_status, work));
+    hipLaunchKernelGGL(auto_clips_kernel, dim3(cdiv((size_t)cnt, 64)), dim3(64), 0, st, cnt, P.au, (float)q.bleach_clip_min,
+                       (float)q.bleach_clip_med, (float)q.bleach_clip_max, std::log1p(1.0), edges, indices, otsu_status, nonfinite,
+                       !q.keep_uniform && !q.log_output, varies, clips, status);
+    return launch_check("auto_clips_kernel");
+}
+
+int run_chunk(Plan& P, hipStream_t st, const void* in, const float* flat, void* out, int cnt, i64 t0) {
     const mi_pystripe_info& I = P.info;
     const mi_pystripe_params& q = P.prm;
     float* sc = P.scratch.as<float>();
@@ -1187,11 +1421,28 @@ int run_chunk(Plan& P, hipStream_t st, const void* in, const float* flat, void* 
     if (P.pre) {
         const int by = q.down_y > 0 ? q.down_y : 1, bx = q.down_x > 0 ? q.down_x : 1;
         const dim3 grid(cdiv(I.nx, 64), cdiv(I.ny, 4), cnt);
-        hipLaunchKernelGGL(pre_kernel, grid, dim3(256), 0, st, src, q.use_flat ? flat : nullptr, by, bx, q.down_method, buf(P.off_stage), I.ny, I.nx);
-        MI_TRY(launch_check("pre_kernel"));
+        const float* fl = q.use_flat ? flat : nullptr;
+        if (q.down_y > 0 && q.down_method == MI_PS_DOWN_MEDIAN) {
+            const int n = by * bx;
+            if (n <= 4) MI_TRY(launch_pre_median<4>(st, grid, src, fl, by, bx, buf(P.off_stage), I.ny, I.nx));
+            else if (n <= 8) MI_TRY(launch_pre_median<8>(st, grid, src, fl, by, bx, buf(P.off_stage), I.ny, I.nx));
+            else if (n <= 16) MI_TRY(launch_pre_median<16>(st, grid, src, fl, by, bx, buf(P.off_stage), I.ny, I.nx));
+            else if (n <= 32) MI_TRY(launch_pre_median<32>(st, grid, src, fl, by, bx, buf(P.off_stage), I.ny, I.nx));
+            else MI_TRY(launch_pre_median<64>(st, grid, src, fl, by, bx, buf(P.off_stage), I.ny, I.nx));
+        } else {
+            hipLaunchKernelGGL(pre_kernel, grid, dim3(256), 0, st, src, fl, by, bx, q.down_method, buf(P.off_stage), I.ny, I.nx);
+            MI_TRY(launch_check("pre_kernel"));
+        }
         src = Src{buf(P.off_stage), (i64)P.sz_stage, MI_PS_F32, I.ny, I.nx, I.nx, 0, MAP_IDENTITY, 0};
     }
     Sink k{};
+    if (P.au) {
+        float* clips = P.clips_buf.as<float>() + 3 * t0;
+        int* status = P.status_buf.as<int>() + t0;
+        MI_TRY(run_auto_clips(P, st, src, cnt, varies, clips, status));
+        P.bq.clips = clips;
+        k.clip_status = status;
+    }
     k.out = out;
     k.tile_stride = (i64)I.out_ny * I.out_nx;
     k.ny = I.ny; k.nx = I.nx; k.pad = I.base_pad;
@@ -1222,6 +1473,7 @@ int run_chunk(Plan& P, hipStream_t st, const void* in, const float* flat, void* 
         kL.out = buf(P.off_L);
         kL.tile_stride = (i64)P.sz_L;
         kL.log_out = 1;
+        kL.clip_status = nullptr;
     }
     const int Lv = I.levels, LT = P.L;
     const float* tab = P.tab_buf.as<float>();
@@ -1351,6 +1603,7 @@ extern "C" int mi_pystripe_plan_create(int dev, int ny, int nx, int in_dtype, co
     P->f = mi::make_filters();
     int rc = mi::derive(ny, nx, in_dtype, *params, *P);
     if (rc == MI_OK) rc = mi::build_tables(*P);
+    if (rc == MI_OK) rc = mi::upload_log_table(*P, nullptr);
     if (rc != MI_OK) {
         delete P;
         return rc;
@@ -1393,6 +1646,7 @@ extern "C" int mi_pystripe_plan_create_wavelet(int dev, int ny, int nx, int in_d
     int rc = mi::derive(ny, nx, in_dtype, *params, *P);
     if (rc == MI_OK) rc = mi::build_tables(*P);
     if (rc == MI_OK) rc = mi::upload_filter_table(*P, rec_lo);
+    if (rc == MI_OK) rc = mi::upload_log_table(*P, nullptr);
     if (rc != MI_OK) {
         delete P;
         return rc;
@@ -1415,6 +1669,35 @@ extern "C" int mi_pystripe_plan_info(void* plan, mi_pystripe_info* info) {
     return MI_OK;
 }
 
+extern "C" int mi_pystripe_plan_set_log_table(void* plan, const float* table, int ncodes) {
+    MI_REQUIRE(plan && table, "mi_pystripe_plan_set_log_table: null pointer");
+    Plan& P = *static_cast<Plan*>(plan);
+    MI_REQUIRE(P.ncodes > 0, "mi_pystripe_plan_set_log_table: the plan estimates no clips of an integer tile");
+    MI_REQUIRE(ncodes == P.ncodes, "mi_pystripe_plan_set_log_table: %d codes, the plan's tiles have %d", ncodes, P.ncodes);
+    MI_TRY(mi::use_device(P.dev));
+    MI_HIP(hipDeviceSynchronize());   // a run that reads the table may still be under way
+    return mi::upload_log_table(P, table);
+}
+
+extern "C" int mi_pystripe_plan_clips(void* plan, float* clips_host, int* status_host, int n) {
+    MI_REQUIRE(plan, "mi_pystripe_plan_clips: null pointer");
+    Plan& P = *static_cast<Plan*>(plan);
+    MI_REQUIRE(P.bleach, "mi_pystripe_plan_clips: the plan has no bleach correction");
+    MI_REQUIRE(n >= 0 && n <= P.last_count, "mi_pystripe_plan_clips: %d tiles, the last run had %lld", n, (long long)P.last_count);
+    if (n == 0) return MI_OK;
+    if (!P.au) {
+        for (int t = 0; t < n; ++t) {
+            if (clips_host) { clips_host[3 * t] = P.bq.lo; clips_host[3 * t + 1] = P.bq.med; clips_host[3 * t + 2] = P.bq.hi; }
+            if (status_host) status_host[t] = MI_PS_CLIPS_OK;
+        }
+        return MI_OK;
+    }
+    MI_TRY(mi::use_device(P.dev));
+    if (clips_host) MI_HIP(hipMemcpy(clips_host, P.clips_buf.p, 3 * sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+    if (status_host) MI_HIP(hipMemcpy(status_host, P.status_buf.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
 extern "C" int mi_pystripe_run(void* plan, void* stream, const void* in, const void* flat, void* out, int64_t count) {
     MI_REQUIRE(plan && in && out, "mi_pystripe_run: null pointer");
     MI_REQUIRE(count >= 0, "mi_pystripe_run: count %lld", (long long)count);
@@ -1430,14 +1713,23 @@ extern "C" int mi_pystripe_run(void* plan, void* stream, const void* in, const v
         P.cap = 0;
         MI_TRY(P.scratch.alloc(std::max<size_t>(P.info.scratch_bytes_per_tile * (size_t)want, 16)));
         MI_TRY(P.varies.alloc(sizeof(int) * (size_t)want));
+        if (P.au) MI_TRY(P.auto_buf.alloc(mi::kAutoBytesPerTile * (size_t)want));
         P.cap = want;
     }
+    if (P.au && count > P.clips_cap) {
+        MI_HIP(hipStreamSynchronize(st));
+        P.clips_cap = 0;
+        MI_TRY(P.clips_buf.alloc(3 * sizeof(float) * (size_t)count));
+        MI_TRY(P.status_buf.alloc(sizeof(int) * (size_t)count));
+        P.clips_cap = count;
+    }
+    P.last_count = count;
     const size_t in_bytes = (size_t)P.in_ny * P.in_nx * (P.in_dtype == MI_PS_U8 ? 1 : P.in_dtype == MI_PS_U16 ? 2 : 4);
     const size_t out_bytes = (size_t)P.info.out_ny * P.info.out_nx * (P.info.out_dtype == MI_PS_U8 ? 1 : P.info.out_dtype == MI_PS_U16 ? 2 : 4);
     for (int64_t t0 = 0; t0 < count; t0 += P.cap) {
         const int cnt = (int)std::min<int64_t>(P.cap, count - t0);
         MI_TRY(mi::run_chunk(P, st, static_cast<const char*>(in) + (size_t)t0 * in_bytes, static_cast<const float*>(flat),
-                             static_cast<char*>(out) + (size_t)t0 * out_bytes, cnt));
+                             static_cast<char*>(out) + (size_t)t0 * out_bytes, cnt, t0));
     }
     return MI_OK;
 }

@@ -12,6 +12,7 @@
 
 #include "mi_internal.h"
 #include "mi_thresholds.h"
+#include "thresholds_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -27,12 +28,7 @@ constexpr int kU16Threads = 1024;    // u16 codes: one work-group per CU, half o
 constexpr int kU16Span = 32768;      // counters of one pass: 128 KiB of the CU's 160
 constexpr i64 kMaxSamples = 1ll << 38;   // per image: keeps the 32-bit LDS counters of one work-group from overflowing
 
-// float -> unsigned whose order is the floats' order for either sign
-__device__ __forceinline__ unsigned float_key(float f) {
-    const unsigned b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_float(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+using namespace histdev;   // float_key, key_float, wave_count, hist_bin (thresholds_dev.h)
 
 template <class T> struct Unpack;
 template <> struct Unpack<float> {
@@ -75,18 +71,6 @@ template <class T, class F> __device__ __forceinline__ void for_each_sample(cons
         const i64 e = threadIdx.x;
         if (e < head) f(p[e]);
         if (tail_at + e < n) f(p[tail_at + e]);
-    }
-}
-
-// One count into an LDS histogram.  The lanes that hold the same bin as the wave's first active lane add once, together: microscopy
-// slices put most samples into a few bins, and 64 atomics on one address run one after the other.
-__device__ __forceinline__ void wave_count(unsigned* h, int b) {
-    const int lead = __builtin_amdgcn_readfirstlane(b);
-    if (b == lead) {
-        const u64 m = __ballot(1);
-        if ((int)(threadIdx.x & 63u) == __ffsll((long long)m) - 1) atomicAdd(&h[lead], (unsigned)__popcll(m));
-    } else {
-        atomicAdd(&h[b], 1u);
     }
 }
 
@@ -164,11 +148,7 @@ __global__ void __launch_bounds__(kThreads) hist256_kernel(const float* base, i6
     const float scale = 256.0f / (e[MI_HIST_BINS] - e0);
     unsigned* mine = h[t >> 6];
     for_each_sample<float>(base, img, n, [&](float v) {
-        int b = (int)((v - e0) * scale);   // an estimate: the edges decide
-        b = min(max(b, 0), MI_HIST_BINS - 1);
-        while (b > 0 && v < e[b]) --b;
-        while (b < MI_HIST_BINS - 1 && v >= e[b + 1]) ++b;
-        wave_count(mine, b);
+        wave_count(mine, hist_bin(e, e0, scale, v));
     });
     __syncthreads();
     unsigned sum = 0;
@@ -350,6 +330,26 @@ unsigned stream_blocks(i64 items_per_thread_unit, int threads, unsigned cap) {
 }
 
 }  // namespace
+
+int hist_init_launch(hipStream_t s, unsigned* keys, int* nonfinite, unsigned long long* counts, int count) {
+    hipLaunchKernelGGL(hist_init_kernel, dim3(count), dim3(kThreads), 0, s, keys, nonfinite, counts);
+    return launch_check("hist_init_kernel");
+}
+
+int hist_edges_launch(hipStream_t s, unsigned* keys, float* edges, int count) {
+    hipLaunchKernelGGL(edges_kernel, dim3(count), dim3(kThreads), 0, s, keys, edges);
+    return launch_check("edges_kernel");
+}
+
+int multiotsu_launch(hipStream_t s, const unsigned long long* counts, int count, int classes, int* indices, int* nvalues, int* status,
+                     unsigned long long* work) {
+    MI_HIP(hipMemsetAsync(work, 0, sizeof(unsigned long long) * (size_t)count, s));
+    hipLaunchKernelGGL(otsu_search_kernel, dim3(kSearchBlocks, count), dim3(kThreads), 0, s, counts, classes, indices, nvalues, status, work);
+    MI_TRY(launch_check("otsu_search_kernel"));
+    hipLaunchKernelGGL(otsu_finish_kernel, dim3(cdiv((size_t)count, 64)), dim3(64), 0, s, count, classes, work, status, indices);
+    return launch_check("otsu_finish_kernel");
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -365,13 +365,11 @@ extern "C" int mi_hist256_f32(int device, void* stream, const float* images, int
     MI_REQUIRE(((uintptr_t)counts % 8) == 0, "mi_hist256_f32: counts must be 8-byte aligned");
     hipStream_t s = as_stream(stream);
     unsigned* keys = reinterpret_cast<unsigned*>(range);
-    hipLaunchKernelGGL(hist_init_kernel, dim3(count), dim3(kThreads), 0, s, keys, nonfinite, counts);
-    MI_TRY(launch_check("hist_init_kernel"));
+    MI_TRY(hist_init_launch(s, keys, nonfinite, counts, count));
     const dim3 grid(stream_blocks(n / 4 + 1, kThreads * 4, 2048), count);
     hipLaunchKernelGGL(minmax_kernel, grid, dim3(kThreads), 0, s, images, (i64)n, keys, nonfinite);
     MI_TRY(launch_check("minmax_kernel"));
-    hipLaunchKernelGGL(edges_kernel, dim3(count), dim3(kThreads), 0, s, keys, edges);
-    MI_TRY(launch_check("edges_kernel"));
+    MI_TRY(hist_edges_launch(s, keys, edges, count));
     hipLaunchKernelGGL(hist256_kernel, grid, dim3(kThreads), 0, s, images, (i64)n, edges, nonfinite, counts);
     return launch_check("hist256_kernel");
 }
@@ -408,10 +406,5 @@ extern "C" int mi_multiotsu_search(int device, void* stream, const unsigned long
     MI_REQUIRE(((uintptr_t)counts % 8) == 0 && ((uintptr_t)work % 8) == 0, "mi_multiotsu_search: counts and work must be 8-byte aligned");
     MI_REQUIRE(((uintptr_t)indices % 4) == 0 && ((uintptr_t)nvalues % 4) == 0 && ((uintptr_t)status % 4) == 0,
                "mi_multiotsu_search: int buffers must be 4-byte aligned");
-    hipStream_t s = as_stream(stream);
-    MI_HIP(hipMemsetAsync(work, 0, sizeof(unsigned long long) * (size_t)count, s));
-    hipLaunchKernelGGL(otsu_search_kernel, dim3(kSearchBlocks, count), dim3(kThreads), 0, s, counts, classes, indices, nvalues, status, work);
-    MI_TRY(launch_check("otsu_search_kernel"));
-    hipLaunchKernelGGL(otsu_finish_kernel, dim3(cdiv((size_t)count, 64)), dim3(64), 0, s, count, classes, work, status, indices);
-    return launch_check("otsu_finish_kernel");
+    return multiotsu_launch(as_stream(stream), counts, count, classes, indices, nvalues, status, work);
 }

@@ -11,11 +11,12 @@ tiles, which go through every kernel launch together (include/mi_pystripe.h).  T
 an error.
 
 What is computed (reference line numbers in include/mi_pystripe.h): uniform tile -> zeros; flat field; ``down_sample`` (max / min /
-mean, zero-padded blocks like skimage's ``block_reduce``); ``filter_streaks`` = log1p, numpy padding (reflect / wrap / symmetric /
+mean / median, zero-padded blocks like skimage's ``block_reduce``); ``filter_streaks`` = log1p, numpy padding (reflect / wrap / symmetric /
 edge), wavelet decomposition (``wavelet=``: 'db9', the pipeline's choice; 'haar' / 'db1' .. 'db20'; or any orthogonal wavelet of up
 to 128 taps as an object with ``rec_lo`` -- ``pywt.Wavelet("coif15")`` -- or the coefficients themselves; ``wavelets.py``), the
 packed-position Gaussian notch on cH (and cV when ``bidirectional``), reconstruction, crop,
-bleach correction (``bleach_correction_frequency`` with the three clips given, in log1p units: the log-domain image divided by a
+bleach correction (``bleach_correction_frequency`` with the three clips in log1p units, each given or, when None, estimated per tile
+on the device by the four-class multi-Otsu of the log image as the reference does: the log-domain image divided by a
 zero-phase first-order Butterworth low-pass of its clipped copy -- row by row, or, with ``bleach_correction_max_method``, the outer
 product of the filtered row and column maxima -- and rescaled by that copy's maximum; it also runs alone, at ``sigma=(0, 0)``),
 expm1, rint + clip for integer tiles; ``dark``; ``lightsheet`` (pystripe/lightsheet_correct.py: local percentiles on two sub-grids,
@@ -28,13 +29,16 @@ Departures, all stated in INTEGRATION.md:
   * ``gaussian_filter_2d`` is accepted and does nothing, as in the reference (its GaussianBlur result is discarded);
   * ``lightsheet=True`` on a tile narrower than ``artifact_length`` or with an extent below 25 is refused (the reference returns
     zeros for a uniform such tile and divides by zero otherwise);
-  * refused by name: ``bleach_correction_frequency`` without all three clips (the automatic ones need ``threshold_multiotsu``),
-    ``enable_masking``, ``exclude_dark_edges_set_them_to_zero``,
-    ``new_size`` in ``process_img`` (``batch_filter`` takes it), a ``new_size`` that needs skimage's Gaussian pre-filter (the tile
+  * ``extended=True`` (``process_img``, ``filter_streaks``, ``batch_filter``, ``make_params``; default False) opens what these entry
+    points refused by name before it existed and still refuse without it: a frequency without all three clips (the missing ones are
+    then estimated per tile), ``down_sample_method='median'``, ``new_size`` in ``process_img``, a ``threshold``;
+  * refused by name also with it: ``enable_masking``, ``exclude_dark_edges_set_them_to_zero``,
+    a ``new_size`` that needs skimage's Gaussian pre-filter (the tile
     shape below ``new_size`` as tuples with an axis that shrinks) or meets an integer tile with a float ``d_type``, ``.dcimg`` input,
-    ``down_sample_method='median'``, a wavelet NAME without a built-in table (``'coif15'``: hand in
-    the coefficients instead), biorthogonal wavelets, other padding modes, a ``threshold``
-    (``use_thresholding`` is never set on this path; ``crossover`` has no effect there either);
+    a median ``down_sample`` over blocks of more than 64 samples, a wavelet NAME without a built-in table (``'coif15'``: hand in
+    the coefficients instead), biorthogonal wavelets, other padding modes, a ``threshold`` of 0 or less with ``sigma1 == 0``
+    (a ``threshold`` above 0 has no effect: ``use_thresholding`` is never set on this path, nor has ``crossover``; 0 or less runs the
+    single ``sigma1`` pass);
   * accepted and ignored: ``workers``, ``threads_per_gpu``, ``timeout``, ``gpu_semaphore``, ``z_step``, ``print_input_file_names``,
     ``verbose``.
 The command line takes the reference's LONG option names with plain ``store_true`` flags (the bleach options, which the reference's
@@ -122,17 +126,26 @@ def _refuse(name, value, why):
 
 
 def _check_unsupported(kw):
-    """Raises NotImplementedError naming the first option this build does not do."""
-    if kw.get("bleach_correction_frequency") is not None and any(kw.get(name) is None for name in BLEACH_CLIPS):
-        _refuse("bleach_correction_frequency", kw["bleach_correction_frequency"],
-                "bleach_correction_clip_min / _med / _max must be given: threshold_multiotsu is not built")
+    """Raises NotImplementedError naming the first option this build does not do.  Without ``extended=True`` that includes what the
+    entry points refused before the option existed: a frequency without all three clips, ``new_size`` in ``process_img``, a
+    ``threshold``."""
+    if not kw.get("extended"):
+        if kw.get("bleach_correction_frequency") is not None and any(kw.get(name) is None for name in BLEACH_CLIPS):
+            _refuse("bleach_correction_frequency", kw["bleach_correction_frequency"],
+                    "bleach_correction_clip_min / _med / _max must be given: the clips that are left out are estimated per tile "
+                    "(threshold_multiotsu of the log image) with extended=True only")
+        if kw.get("new_size") is not None:
+            _refuse("new_size", kw["new_size"], "process_img resizes with extended=True only; batch_filter (and resize_tiles) do")
+        if kw.get("threshold") is not None:
+            _refuse("threshold", kw["threshold"], "accepted with extended=True only (the thresholding dual-band path is not built)")
     for name in ("enable_masking", "exclude_dark_edges_set_them_to_zero"):
         if kw.get(name):
             _refuse(name, kw[name], "not built (needs OpenCV / scikit-image semantics)")
-    if kw.get("new_size") is not None:
-        _refuse("new_size", kw["new_size"], "process_img does not resize; batch_filter (and resize_tiles) do")
-    if kw.get("threshold") is not None:
-        _refuse("threshold", kw["threshold"], "the thresholding dual-band path is not built")
+    threshold = kw.get("threshold")
+    if threshold is not None and threshold <= 0 and "sigma" in kw:
+        s1, s2 = _sigma_pair(kw["sigma"])
+        if s1 == 0 and s2 != 0:
+            _refuse("threshold", threshold, f"with sigma={kw['sigma']!r} the reference runs filter_subband at sigma 0; not built")
     if kw.get("log1p_normalization_needed") is False:
         _refuse("log1p_normalization_needed", False, "only the log1p path is built")
 
@@ -144,17 +157,23 @@ _FLOATS = (float, np.float32, np.float64)
 def check_bleach(shape, frequency, clip_min, clip_med, clip_max, max_method=False, down_sample=None):
     """What the reference raises for these bleach-correction arguments on a tile of ``shape``, from the values alone: the asserts of
     correct_bleaching (pystripe/core.py:524-528) as AssertionError, then butter's ValueError for a frequency of 1 or more, then
-    sosfiltfilt's for a filtered line of 6 samples or fewer (the rows; with ``max_method`` also the column of row maxima)."""
+    sosfiltfilt's for a filtered line of 6 samples or fewer (the rows; with ``max_method`` also the column of row maxima).  A clip
+    that is None is estimated per tile on the device (``threshold_multiotsu`` of the log image): the checks that involve it run
+    there, on the estimate; those between given clips run here."""
     def require(ok, what):
         if not ok:
             raise AssertionError(what)
     require(isinstance(frequency, _FLOATS) and frequency > 0, f"bleach_correction_frequency={frequency!r}: a float above 0 is expected")
-    require(isinstance(clip_min, _FLOATS) and clip_min >= 0, f"bleach_correction_clip_min={clip_min!r}: a float, 0 or more, is expected")
-    require(isinstance(clip_med, _FLOATS) and clip_med > clip_min,
-            f"bleach_correction_clip_med={clip_med!r}: a float above bleach_correction_clip_min={clip_min!r} is expected")
-    require(isinstance(clip_max, _FLOATS) and clip_max > clip_min,
-            f"bleach_correction_clip_max={clip_max!r}: a float above bleach_correction_clip_min={clip_min!r} is expected")
-    require(clip_max > clip_med, f"bleach_correction_clip_max={clip_max!r} is not above bleach_correction_clip_med={clip_med!r}")
+    if clip_min is not None:
+        require(isinstance(clip_min, _FLOATS) and clip_min >= 0, f"bleach_correction_clip_min={clip_min!r}: a float, 0 or more, is expected")
+    if clip_med is not None:
+        require(isinstance(clip_med, _FLOATS) and (clip_min is None or clip_med > clip_min),
+                f"bleach_correction_clip_med={clip_med!r}: a float above bleach_correction_clip_min={clip_min!r} is expected")
+    if clip_max is not None:
+        require(isinstance(clip_max, _FLOATS) and (clip_min is None or clip_max > clip_min),
+                f"bleach_correction_clip_max={clip_max!r}: a float above bleach_correction_clip_min={clip_min!r} is expected")
+        require(clip_med is None or clip_max > clip_med,
+                f"bleach_correction_clip_max={clip_max!r} is not above bleach_correction_clip_med={clip_med!r}")
     if not frequency < 1:
         raise ValueError(f"Digital filter critical frequencies must be 0 < Wn < 1 (bleach_correction_frequency={frequency!r})")
     shape = tuple(int(v) for v in shape[-2:])
@@ -204,8 +223,9 @@ def make_params(in_dtype, flat=False, down_sample=None, down_sample_method="max"
                 padding_mode="reflect", bidirectional=False, dark=0, rotate=0, flip_upside_down=False, convert_to_16bit=False,
                 convert_to_8bit=False, bit_shift_to_right=8, d_type=None, log_output=False, keep_uniform=False, max_batch=0,
                 bleach_correction_frequency=None, bleach_correction_max_method=False, bleach_correction_clip_min=None,
-                bleach_correction_clip_med=None, bleach_correction_clip_max=None):
-    """mi_pystripe_params for process_img's options.  Everything the C side cannot name itself is refused here."""
+                bleach_correction_clip_med=None, bleach_correction_clip_max=None, extended=False):
+    """mi_pystripe_params for process_img's options.  Everything the C side cannot name itself is refused here.  ``extended=True``
+    takes a clip that is None (NaN in the struct: estimated per tile) and the median down-sampling."""
     s1, s2 = _sigma_pair(sigma)
     filt = (s1, s2) > (0, 0)
     wobj = None
@@ -228,13 +248,15 @@ def make_params(in_dtype, flat=False, down_sample=None, down_sample_method="max"
     p.bidirectional = int(bool(bidirectional))
     if down_sample is not None:
         method = str(down_sample_method).lower()
-        if method == "median":
-            _refuse("down_sample_method", down_sample_method, "max, min and mean are built")
+        if method == "median" and not extended:
+            _refuse("down_sample_method", down_sample_method, "max, min and mean are built; the median with extended=True")
         if method not in capi.PS_DOWN:
             print(f"unsupported down-sampling method: {down_sample_method}")
             raise RuntimeError(f"unsupported down-sampling method: down_sample_method={down_sample_method!r}")
         p.down_y, p.down_x = (int(d) if d is not None else 1 for d in down_sample)
         p.down_method = capi.PS_DOWN[method]
+        if method == "median" and p.down_y * p.down_x > capi.PS_MEDIAN_MAX_BLOCK:
+            _refuse("down_sample", down_sample, f"down_sample_method='median' is built for blocks of up to {capi.PS_MEDIAN_MAX_BLOCK} samples")
     p.use_flat = int(bool(flat))
     p.dark = float(dark) if dark is not None and dark > 0 else 0.0
     if convert_to_16bit and convert_to_8bit:
@@ -257,9 +279,9 @@ def make_params(in_dtype, flat=False, down_sample=None, down_sample_method="max"
     if bleach_correction_frequency is not None:
         clips = dict(bleach_correction_clip_min=bleach_correction_clip_min, bleach_correction_clip_med=bleach_correction_clip_med,
                      bleach_correction_clip_max=bleach_correction_clip_max)
-        _check_unsupported(dict(clips, bleach_correction_frequency=bleach_correction_frequency))
+        _check_unsupported(dict(clips, bleach_correction_frequency=bleach_correction_frequency, extended=extended))
         p.bleach_frequency = float(bleach_correction_frequency)
-        p.bleach_clip_min, p.bleach_clip_med, p.bleach_clip_max = (float(clips[name]) for name in BLEACH_CLIPS)
+        p.bleach_clip_min, p.bleach_clip_med, p.bleach_clip_max = (math.nan if clips[name] is None else float(clips[name]) for name in BLEACH_CLIPS)
         p.bleach_max_method = int(bool(bleach_correction_max_method))
     p.wavelet = wobj   # a Python attribute beside the C fields: None, or the OrthogonalWavelet that derive / Plan hand to the C side
     return p
@@ -311,6 +333,21 @@ class Plan:
         capi.check(capi.lib().mi_pystripe_plan_info(self._h, C.byref(self.info)))
         self.out_shape = (self.info.out_ny, self.info.out_nx)
         self.out_dtype = _CODE_NP[self.info.out_dtype]
+        self._last_n = 0
+        if params.bleach_auto and self.info.integer_kind:
+            # numpy's float32 log1p of every code decides the bins of the automatic clips, not the device's log1pf
+            from .thresholds import log_table
+            table = np.ascontiguousarray(log_table(256 if self.in_dtype == np.uint8 else 65536), dtype=np.float32)
+            capi.check(capi.lib().mi_pystripe_plan_set_log_table(self._h, table.ctypes.data, table.size))
+
+    def clips(self, n=None):
+        """(clips float32 [n, 3], status int32 [n]) of the first ``n`` tiles (default: all) of the last ``run``: the triple
+        (min, med, max) in log1p units the bleach correction used -- min raised to log1p(1) -- and capi.PS_CLIPS_*.  The caller has
+        synchronised the stream of that run."""
+        n = self._last_n if n is None else int(n)
+        clips, status = np.empty((n, 3), np.float32), np.empty((n,), np.int32)
+        capi.check(capi.lib().mi_pystripe_plan_clips(self._h, clips.ctypes.data, status.ctypes.data, n))
+        return clips, status
 
     def run(self, tiles, flat=None, out=None):
         import torch
@@ -328,6 +365,7 @@ class Plan:
             fp = flat.data_ptr()
         with torch.cuda.device(tiles.device):
             capi.check(capi.lib().mi_pystripe_run(self._h, capi.current_stream_ptr(tiles.device), tiles.data_ptr(), fp, out.data_ptr(), n))
+        self._last_n = n
         return out
 
     def close(self):
@@ -711,7 +749,26 @@ def _lightsheet_opts(lightsheet, shape, down_sample, artifact_length, background
                 lightsheet_vs_background=lightsheet_vs_background)
 
 
-def _run_tiles(img, flat, device, lightsheet=None, **opts):
+def raise_for_clips(plan, verbose=False):
+    """After a synchronised run of ``plan`` (a Plan with automatic clips): what the reference raises for the first tile whose clips
+    could not be used -- threshold_multiotsu's / numpy.histogram's ValueError, the AssertionError of correct_bleaching -- naming the
+    tile's index in the stack and the triple.  ``verbose`` prints every tile's triple through expm1, as filter_streaks does."""
+    clips, status = plan.clips()
+    for t, (triple, st) in enumerate(zip(clips, status)):
+        what = f"tile {t}: bleach_correction_clip_min, _med, _max = {tuple(float(v) for v in triple)}"
+        if st == capi.PS_CLIPS_TOO_FEW:
+            raise ValueError(f"{what}: after discretization into bins, the log image has fewer than 4 different values; it cannot be "
+                             "thresholded in 4 classes")
+        if st == capi.PS_CLIPS_NONFINITE:
+            raise ValueError(f"{what}: autodetected range of the log image is not finite")
+        if st == capi.PS_CLIPS_ORDER:
+            raise AssertionError(f"{what}: 0 <= clip_min < clip_med < clip_max is expected (correct_bleaching)")
+        if verbose and st == capi.PS_CLIPS_OK:
+            lo, med, hi = (float(np.expm1(v)) for v in triple)
+            print(f"bleach correction is applied: tile {t}, clip_min={lo}, clip_med={med}, clip_max={hi}")
+
+
+def _run_tiles(img, flat, device, lightsheet=None, verbose=False, **opts):
     """img: 2-D tile or [n, ny, nx] stack, numpy or device tensor -> the same kind of container."""
     import torch
     tiles, single, is_tensor, in_dtype = _as_stack(img, device)
@@ -727,31 +784,44 @@ def _run_tiles(img, flat, device, lightsheet=None, **opts):
     try:
         out = plan.run(tiles, flat_t)
         torch.cuda.synchronize(tiles.device)
+        if plan.head.params.bleach_auto:
+            raise_for_clips(plan.head, verbose)
     finally:
         plan.close()
     out = out[0] if single else out
     return out if is_tensor else out.cpu().numpy()
 
 
+def _single_band(sigma, threshold):
+    """``sigma`` as filter_streak_dual_band (pystripe/core.py:943) uses it on this path, where use_thresholding is never set:
+    unchanged for ``threshold`` None or above 0; a threshold of 0 or less runs the single sigma1 pass."""
+    s1, s2 = _sigma_pair(sigma)
+    if threshold is None or threshold > 0 or s1 == s2:
+        return sigma
+    return (s1, s1)
+
+
 def filter_streaks(img, sigma=(250, 250), level=0, wavelet="db9", crossover=10, threshold=None, padding_mode="wrap",
                    bidirectional=False, gpu_semaphore=None, bleach_correction_frequency=None, bleach_correction_max_method=False,
                    bleach_correction_clip_min=None, bleach_correction_clip_med=None, bleach_correction_clip_max=None,
                    log1p_normalization_needed=True, enable_masking=False, close_steps=50, open_steps=500, verbose=False, device=None,
-                   log_output=False):
+                   log_output=False, extended=False):
     """pystripe/core.py:982 on the GPU.  ``crossover`` has no effect on this path (as in the reference).  ``log_output=True`` returns
-    the float32 image just before ``expm1`` (an addition, for tests).  The bleach correction needs the three clips (log1p units);
-    with ``sigma=(0, 0)`` it runs alone."""
+    the float32 image just before ``expm1`` (an addition, for tests).  The bleach correction takes the three clips in log1p units; one
+    left None is estimated per tile (``threshold_multiotsu(log1p(img), classes=4)``) and a tile it cannot be estimated for raises as in
+    the reference (``raise_for_clips``).  With ``sigma=(0, 0)`` the correction runs alone."""
     _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, bleach_correction_clip_min=bleach_correction_clip_min,
                             bleach_correction_clip_med=bleach_correction_clip_med, bleach_correction_clip_max=bleach_correction_clip_max,
-                            enable_masking=enable_masking, threshold=threshold, log1p_normalization_needed=log1p_normalization_needed))
-    s1, s2 = _sigma_pair(sigma)
+                            enable_masking=enable_masking, threshold=threshold, sigma=sigma, extended=extended,
+                            log1p_normalization_needed=log1p_normalization_needed))
+    s1, s2 = _sigma_pair(_single_band(sigma, threshold))
     if s1 == s2 == 0 and bleach_correction_frequency is None:
         return img
     wavelet = _early_wavelet((s1, s2), wavelet)
     bleach = _bleach_opts(img.shape, None, bleach_correction_frequency, bleach_correction_max_method, bleach_correction_clip_min,
                           bleach_correction_clip_med, bleach_correction_clip_max)
     return _run_tiles(img, None, device, sigma=(s1, s2), level=level, wavelet=wavelet, padding_mode=padding_mode, bidirectional=bidirectional,
-                      keep_uniform=True, log_output=log_output, **bleach)
+                      keep_uniform=True, log_output=log_output, verbose=verbose, extended=extended, **bleach)
 
 
 def process_img(img, flat=None, gaussian_filter_2d=False, down_sample=None, down_sample_method="max", tile_size=None, new_size=None,
@@ -760,17 +830,23 @@ def process_img(img, flat=None, gaussian_filter_2d=False, down_sample=None, down
                 bleach_correction_clip_min=None, bleach_correction_clip_med=None, bleach_correction_clip_max=None,
                 bleach_correction_max_method=False, log1p_normalization_needed=True, dark=0, lightsheet=False, artifact_length=150,
                 background_window_size=200, percentile=0.25, lightsheet_vs_background=2.0, rotate=0, flip_upside_down=False,
-                convert_to_16bit=False, convert_to_8bit=False, bit_shift_to_right=8, d_type=None, verbose=False, device=None):
+                convert_to_16bit=False, convert_to_8bit=False, bit_shift_to_right=8, d_type=None, verbose=False, device=None,
+                extended=False):
     """pystripe/core.py:1190 on the GPU, the reference's keywords and defaults (so ``wavelet`` must be given when ``sigma`` asks for the
     filter: the default NAME 'coif15' has no table here; ``wavelet=pywt.Wavelet("coif15")`` or its ``rec_lo`` is taken).
     ``gaussian_filter_2d`` does nothing, as in the reference, whose GaussianBlur result is discarded.  ``img`` may be
     a stack [n, ny, nx] of equally shaped tiles (an addition): they go through every launch together.  ``lightsheet=True`` runs
     ``correct_lightsheet`` after ``dark`` as the reference does; a tile too small for one window is refused from its shape alone.
-    ``bleach_correction_frequency`` needs the three clips, in log1p units (the automatic ones are not built)."""
+    The clips of ``bleach_correction_frequency`` are in log1p units; one left None is estimated per tile on the device.  ``new_size``
+    resizes after ``dark`` / ``lightsheet`` as ``batch_filter`` does; ``threshold``: see the module's text."""
     _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, bleach_correction_clip_min=bleach_correction_clip_min,
                             bleach_correction_clip_med=bleach_correction_clip_med, bleach_correction_clip_max=bleach_correction_clip_max,
-                            new_size=new_size, exclude_dark_edges_set_them_to_zero=exclude_dark_edges_set_them_to_zero, threshold=threshold,
-                            log1p_normalization_needed=log1p_normalization_needed))
+                            exclude_dark_edges_set_them_to_zero=exclude_dark_edges_set_them_to_zero, threshold=threshold, sigma=sigma,
+                            new_size=new_size, extended=extended, log1p_normalization_needed=log1p_normalization_needed))
+    sigma = _single_band(sigma, threshold)
+    if new_size is not None:   # the values and the shapes, before anything touches the device
+        shape = tuple(int(v) for v in img.shape[-2:])
+        resize_decision(shape if down_sample is None else calculate_down_sampled_size(shape, down_sample), check_new_size(new_size))
     wavelet = _early_wavelet(sigma, wavelet)
     ls = _lightsheet_opts(lightsheet, img.shape, down_sample, artifact_length, background_window_size, percentile, lightsheet_vs_background)
     bleach = _bleach_opts(img.shape, down_sample, bleach_correction_frequency, bleach_correction_max_method, bleach_correction_clip_min,
@@ -778,7 +854,7 @@ def process_img(img, flat=None, gaussian_filter_2d=False, down_sample=None, down
     return _run_tiles(img, flat, device, lightsheet=ls, down_sample=down_sample, down_sample_method=down_sample_method, sigma=sigma, level=level,
                       wavelet=wavelet, padding_mode=padding_mode, bidirectional=bidirectional, dark=dark, rotate=rotate,
                       flip_upside_down=flip_upside_down, convert_to_16bit=convert_to_16bit, convert_to_8bit=convert_to_8bit,
-                      bit_shift_to_right=bit_shift_to_right, d_type=d_type, **bleach)
+                      bit_shift_to_right=bit_shift_to_right, d_type=d_type, new_size=new_size, verbose=verbose, extended=extended, **bleach)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -870,7 +946,7 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
                  lightsheet=False, artifact_length=150, background_window_size=200, percentile=.25, lightsheet_vs_background=2.0,
                  convert_to_16bit=False, convert_to_8bit=False, bit_shift_to_right=8, continue_process=False, d_type=None, tile_size=None,
                  down_sample=None, new_size=None, print_input_file_names=False, timeout=None, compression=("ADOBE_DEFLATE", 1),
-                 down_sample_method="max", device=None, max_batch=None, stats=None):
+                 down_sample_method="max", device=None, max_batch=None, stats=None, extended=False):
     """pystripe/core.py:1806: every .tif / .tiff / .raw / .png under ``input_path`` (or ``files_list``) -> the same relative path
     under ``output_path`` with a ``.tif`` suffix.  Returns 0.
 
@@ -878,8 +954,8 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
     batch is read and the previous one written on host threads while the device works on the current one.  Under ``torchrun`` every
     rank takes every WORLD_SIZE-th file on its LOCAL_RANK device.  ``continue_process``: a file whose output exists is skipped.  A file
     that cannot be read becomes a zero tile when ``d_type`` and ``tile_size`` are given, else it is skipped with a warning.
-    ``bleach_correction_frequency`` needs the three clips, in log1p units; ``bleach_correction_max_method`` defaults to True here, as
-    in the reference.  ``new_size``: every tile whose own shape after ``down_sample`` differs from it is resized to it after ``dark`` /
+    The clips of ``bleach_correction_frequency`` are in log1p units, one left None is estimated per tile;
+    ``bleach_correction_max_method`` defaults to True here, as in the reference.  ``new_size``: every tile whose own shape after ``down_sample`` differs from it is resized to it after ``dark`` /
     ``lightsheet`` and before the conversion (``resize_decision``, ``resize_tiles``); outputs have that shape, swapped under
     ``rotate`` 90 / 270.  A tile whose shape differs from ``tile_size`` is not resized to ``tile_size``, as in the reference.  ``workers``, ``threads_per_gpu``, ``timeout``, ``z_step``, ``print_input_file_names`` are accepted and ignored.  ``stats`` (a dict)
     receives the seconds spent reading, computing and writing and the file counts."""
@@ -889,7 +965,8 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
         raise TypeError("convert_to_16bit and convert_to_8bit are both set: choose one output format")
     _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, bleach_correction_clip_min=bleach_correction_clip_min,
                             bleach_correction_clip_med=bleach_correction_clip_med, bleach_correction_clip_max=bleach_correction_clip_max,
-                            threshold=threshold))
+                            threshold=threshold, sigma=sigma, extended=extended))
+    sigma = _single_band(sigma, threshold)
     if new_size is not None:   # the values, and the shapes where they are known, before anything touches the device
         new_size = check_new_size(new_size)
         if tile_size is not None:
@@ -920,7 +997,7 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
     opts = dict(down_sample=down_sample, down_sample_method=down_sample_method, sigma=sigma, level=level, wavelet=wavelet,
                 padding_mode=padding_mode, bidirectional=bidirectional, dark=dark, rotate=rotate, flip_upside_down=flip_upside_down,
                 convert_to_16bit=convert_to_16bit, convert_to_8bit=convert_to_8bit, bit_shift_to_right=bit_shift_to_right, d_type=d_type,
-                **_bleach_opts((7, 7), None, *bleach_args))
+                extended=extended, **_bleach_opts((7, 7), None, *bleach_args))
 
     st = dict(read_s=0.0, compute_s=0.0, write_s=0.0, files=len(files), written=0, skipped_existing=0, skipped_unreadable=0, zero_tiles=0)
     todo = []
@@ -1008,6 +1085,8 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
             plan, flat_t = plans[key]
             stack = torch.from_numpy(np.stack([m[0] for m in members])).to(device)
             out = plan.run(stack, flat_t).cpu().numpy()
+            if plan.head.params.bleach_auto:
+                raise_for_clips(plan.head)
             results.append(([m[1] for m in members], out))
         st["compute_s"] += time.perf_counter() - t0
         return results
@@ -1097,9 +1176,12 @@ def _parse_args(argv=None):
     for name, what in (("min", "background vs foreground threshold"), ("med", "intermediate foreground value (it also replaces exact zeros)"),
                        ("max", "largest foreground value")):
         p.add_argument(f"--bleach_correction_clip_{name}", type=float, default=None,
-                       help=f"bleach correction: {what}, in log1p units (log1p of the intensity); all three clips are required unless --estimate_clips fills them")
+                       help=f"bleach correction: {what}, in log1p units (log1p of the intensity); all three clips are required unless --estimate_clips fills them or --extended estimates them per tile")
     p.add_argument("--bleach_correction_max_method", action=argparse.BooleanOptionalAction, default=True,
                    help="bleach correction from the filtered row and column maxima (default) rather than from every filtered row")
+    p.add_argument("--extended", action="store_true",
+                   help="batch_filter(extended=True): a bleach clip that is not given is estimated per tile, --down_sample_method median "
+                        "and --threshold are accepted")
     p.add_argument("--estimate_clips", action="store_true",
                    help="with --bleach_correction_frequency: take the clips that are not given from the slices of --input at 25 %%, 50 %% and "
                         "75 %% of the depth (four-class multi-Otsu of the log1p image, as process_images.py does) and print them")
@@ -1155,7 +1237,7 @@ def main(argv=None):
                       bit_shift_to_right=a.bit_shift_to_right, continue_process=a.continue_process, d_type=a.dtype,
                       tile_size=tuple(a.tile_size) if a.tile_size else None, down_sample=tuple(a.down_sample) if a.down_sample else None,
                       new_size=new_size, down_sample_method=a.down_sample_method, compression=(a.compression_method, a.compression_level),
-                      max_batch=a.max_batch, stats=stats, **clips)
+                      max_batch=a.max_batch, stats=stats, extended=a.extended, **clips)
     print("pystripe: {files} files, {written} written, {skipped_existing} already there, {skipped_unreadable} unreadable, "
           "{zero_tiles} zero tiles; read {read_s:.2f} s, compute {compute_s:.2f} s, write {write_s:.2f} s".format(**stats))
     return rc

@@ -15,12 +15,23 @@
  *   is_uniform_2d          :107-121,  calculate_down_sampled_size :1162-1170
  * skimage.measure.block_reduce (zero padding to a multiple of the block) is restated for max / min / mean.
  *
- * Not built (refused by the Python layer by name): the automatic bleach-correction clips (threshold_multiotsu), masking, dark-edge
+ * skimage.measure.block_reduce with numpy.median: blocks of up to MI_PS_MEDIAN_MAX_BLOCK samples, an even count gives the mean of the
+ * two middle values; a NaN sorts by fminf / fmaxf, not as numpy sorts it.
+ *
+ * Not built (refused by the Python layer by name): masking, dark-edge
  * exclusion, biorthogonal wavelets and wavelets named without a table (the library holds the Daubechies family only; the
- * Python layer takes any other orthogonal wavelet as its coefficients), padding modes other than reflect / wrap / symmetric / edge,
- * the median down-sampling.  The lightsheet correction of process_img :1333-1348 is mi_lightsheet.h; the Python layer runs it between two
- * plans of this header, and so it does with the resize to new_size of batch_filter (:1356-1359), which is mi_tile_resize.h;
- * process_img(new_size=...) itself stays refused.
+ * Python layer takes any other orthogonal wavelet as its coefficients), padding modes other than reflect / wrap / symmetric / edge.
+ * The lightsheet correction of process_img :1333-1348 is mi_lightsheet.h; the Python layer runs it between two
+ * plans of this header, and so it does with the resize to new_size (:1356-1359), which is mi_tile_resize.h.
+ *
+ * Automatic clips (a clip given as NaN; filter_streaks :1066-1077): threshold_multiotsu(log1p(tile), classes=4) per tile, inside the run,
+ * of the tile after flat and down_sample and before padding and the stripe filter; the log image is not stored for it.  Two passes
+ * read the source: the finite range, then numpy.histogram(., 256) with the edges of mi_thresholds.h; the four-class search of
+ * mi_thresholds.h follows, and the thresholds are the float32 centres (edges[i] + edges[i + 1]) / 2 of the bins it names.  For an
+ * integer-kind tile the value of a sample is table[code] (mi_pystripe_plan_set_log_table), so the counts are those of
+ * numpy.histogram(log1p(codes)) exactly; for a float tile it is log1pf on load, as the filter reads it.  Given clips keep their
+ * slot, min is raised to log1p(1), and the asserts of correct_bleaching run on the result.  A tile whose status is 1, 2 or 3 is
+ * written as zeros; the run returns MI_OK, reads nothing back and does not wait.
  *
  * Bleach correction (bleach_frequency > 0), on the float32 log-domain image L (the stripe filter's cropped result, or log1p(tile)
  * when sigma == (0, 0)), just before expm1:
@@ -57,7 +68,20 @@ extern "C" {
 
 typedef enum { MI_PS_U8 = 0, MI_PS_U16 = 1, MI_PS_F32 = 2 } mi_pystripe_dtype;
 typedef enum { MI_PS_REFLECT = 0, MI_PS_WRAP = 1, MI_PS_SYMMETRIC = 2, MI_PS_EDGE = 3 } mi_pystripe_padding;   /* numpy.pad modes */
-typedef enum { MI_PS_DOWN_MAX = 0, MI_PS_DOWN_MIN = 1, MI_PS_DOWN_MEAN = 2 } mi_pystripe_down;
+typedef enum { MI_PS_DOWN_MAX = 0, MI_PS_DOWN_MIN = 1, MI_PS_DOWN_MEAN = 2, MI_PS_DOWN_MEDIAN = 3 } mi_pystripe_down;
+#define MI_PS_MEDIAN_MAX_BLOCK 64   /* samples of a median block (down_y * down_x): they are sorted in registers */
+/* the clips estimated per tile (those given as NaN), as bits: what the Python layer reports as bleach_auto */
+#define MI_PS_AUTO_MIN 1
+#define MI_PS_AUTO_MED 2
+#define MI_PS_AUTO_MAX 4
+/* status of a tile's clips (mi_pystripe_plan_clips) */
+typedef enum {
+    MI_PS_CLIPS_UNIFORM = -1,     /* uniform tile: zeros, nothing estimated */
+    MI_PS_CLIPS_OK = 0,
+    MI_PS_CLIPS_TOO_FEW = 1,      /* fewer than four occupied bins (threshold_multiotsu's ValueError) */
+    MI_PS_CLIPS_ORDER = 2,        /* not 0 <= min < med < max (the asserts of correct_bleaching) */
+    MI_PS_CLIPS_NONFINITE = 3     /* the log image holds a NaN or an infinity (numpy.histogram's ValueError) */
+} mi_pystripe_clip_status;
 #define MI_PS_MAX_LEVELS 24
 #define MI_PS_MAX_TAPS 128
 /* bleach correction: the longest row whose n + 12 doubles fit the LDS of one work-group beside the 16 wave totals of the scan:
@@ -84,7 +108,8 @@ typedef struct {
     int max_batch;             /* tiles that go through one launch (scratch is held for this many); <= 0: 16 */
     int keep_uniform;          /* 1: no uniform-tile rule (filter_streaks called on its own filters a uniform tile like any other) */
     double bleach_frequency;   /* 0: no bleach correction; else butter's Wn, in (0, 1) (1: the Nyquist frequency) */
-    double bleach_clip_min, bleach_clip_med, bleach_clip_max;   /* log1p units: 0 <= min < med < max; min is raised to log1p(1) */
+    double bleach_clip_min, bleach_clip_med, bleach_clip_max;   /* log1p units: 0 <= min < med < max; min is raised to log1p(1); a clip
+                                  that is NaN is estimated per tile ("Automatic clips" above) */
     int bleach_max_method;     /* 1: F is the outer product of the filtered row and column maxima of L */
 } mi_pystripe_params;
 
@@ -118,6 +143,14 @@ int mi_pystripe_derive(int ny, int nx, int in_dtype, const mi_pystripe_params* p
  * float32 on the device when params.use_flat, else NULL.  Tiles are independent: a tile's result does not depend on count or
  * on its place in the batch.  Enqueues on `stream`; the first call (and a call after a larger count) allocates the scratch. */
 int mi_pystripe_run(void* plan, void* stream, const void* in, const void* flat, void* out, int64_t count);
+/* Automatic clips of integer tiles: table[code] = log1p(code) as float32 for code < ncodes (256 for uint8 tiles, 65536 for uint16),
+ * from host memory.  The table, never the device's log1pf, decides a sample's bin.  A plan starts with libm's log1pf; the Python
+ * layer hands in numpy's.  Synchronises.  MI_ERR_INVALID for a plan without automatic clips on an integer tile. */
+int mi_pystripe_plan_set_log_table(void* plan, const float* table, int ncodes);
+/* The clips (clips_host[n][3]: min as used, i.e. raised to log1p(1), med, max) and the mi_pystripe_clip_status (status_host[n]) of
+ * the n tiles of the plan's last run, whatever max_batch did to it; a plan without automatic clips reports its constants and 0.
+ * The caller has synchronised the run's stream.  Either pointer may be NULL. */
+int mi_pystripe_plan_clips(void* plan, float* clips_host, int* status_host, int n);
 /* calculate_pad_size(shape=(ny, nx), sigma) (:681) */
 int mi_pystripe_pad_size(int ny, int nx, double sigma);
 
