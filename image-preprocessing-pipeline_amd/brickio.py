@@ -298,6 +298,58 @@ def load_tiff_series(folder, z0=0, z1=None):
     return vol
 
 
+def _torch_tiff_dtype(dtype):
+    import torch
+    return {np.dtype(np.uint8): torch.uint8, np.dtype(np.uint16): torch.uint16, np.dtype(np.float32): torch.float32}[np.dtype(dtype)]
+
+
+def read_tiff_box_device(files, shape_yx, dtype, y0, y1, x0, x1, device=None, out=None, threads=0):
+    """``read_tiff_box`` with the box in device memory: the strips cross to the device as they are in the files and are inflated
+    there (``mi_tiff_read_box_device``).  Returns a torch tensor ``[n, y1 - y0, x1 - x0]`` of uint8 / uint16 / float32 on ``device``
+    (default: torch's current device); ``out``: such a tensor, contiguous, to read into."""
+    import torch
+    from . import capi
+    capi.require_gpu()
+    n = len(files)
+    tdtype = _torch_tiff_dtype(dtype)
+    if out is None:
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty((n, y1 - y0, x1 - x0), dtype=tdtype, device=dev)
+    if not (out.is_cuda and out.is_contiguous() and out.dtype == tdtype and tuple(out.shape) == (n, y1 - y0, x1 - x0)):
+        raise ValueError("read_tiff_box_device: out must be a contiguous device tensor [n, y1 - y0, x1 - x0] of the files' sample type")
+    paths = (C.c_char_p * n)(*[os.fsencode(str(f)) for f in files])
+    with torch.cuda.device(out.device):
+        capi.check(capi.lib().mi_tiff_read_box_device(out.device.index, capi.current_stream_ptr(out.device), paths, n, int(shape_yx[1]),
+                                                      int(shape_yx[0]), _TIFF_CODES[np.dtype(dtype)], int(y0), int(y1), int(x0), int(x1),
+                                                      out.data_ptr(), int(threads)))
+    return out
+
+
+def load_tiff_series_device(folder, z0=0, z1=None, device=None):
+    """``load_tiff_series`` with a device tensor as result.  When the first file is one the native reader decodes, the series is
+    inflated on the device and every failure of that read is the caller's (a later slice of another shape: ``ValueError``, as
+    ``load_tiff_series`` raises it); there is no second attempt on the host.  Only when the first file is not one of those files is
+    the series read on the host and uploaded."""
+    import torch
+    from . import capi
+    files = list_tiff_series(folder)[z0:z1]
+    if not files:
+        raise RuntimeError(f"no *.tif slices in {folder}")
+    info = tiff_info(files[0])
+    if info is not None and info[2]:
+        (ny, nx), dt, _ = info
+        try:
+            return read_tiff_box_device(files, (ny, nx), dt, 0, ny, 0, nx, device=device)
+        except capi.MiError as e:
+            if "differs from the first slice" in str(e):
+                raise ValueError(str(e)) from e
+            raise
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    return torch.from_numpy(load_tiff_series(folder, z0, z1)).to(dev)
+
+
 def save_tiff_series_device(folder, vol, first_index=1):
     """``save_tiff_series`` for a volume that lies in device memory (a contiguous uint8 / uint16 / float32 CUDA tensor (Z, Y, X)): the
     slices are deflated on the device (``mi_tiff_write_series_device``), the host frames and writes them.  Existing slices are kept."""

@@ -139,5 +139,7 @@ struct PinnedBuf {
 
 // ncc_pair.hip: destroys the pair working sets kept between mi_ncc_mips_batch calls (dev < 0: of every device)
 void ncc_drop_cached_slots(int dev);
+// tiff_inflate.hip: gives up the pinned and device scratch the device TIFF reader keeps between calls (dev < 0: of every device)
+void tiff_inflate_drop_scratch(int dev);
 
 }  // namespace mi

@@ -24,10 +24,13 @@
 
 #include "mi_internal.h"
 #include "mi_tiffio.h"
+#include "tiffio_internal.h"
 
 namespace {
 
 using mi::fail;
+using mi::pread_all;
+using mi::run_jobs;
 
 // ------------------------------------------------------------------------------------------------ deflate: libdeflate or zlib
 struct Deflate {
@@ -122,36 +125,6 @@ int host_cores() {
 }
 int thread_count(int asked, int jobs) { return std::max(1, std::min(asked > 0 ? asked : host_cores(), jobs)); }
 
-// runs job(k, thread) for k < jobs on nt threads; the first error message wins
-template <class F>
-int run_jobs(int jobs, int nt, F&& job) {
-    std::atomic<int> next{0};
-    std::mutex mu;
-    std::string err;
-    auto worker = [&](int t) {
-        for (;;) {
-            const int k = next.fetch_add(1);
-            if (k >= jobs) return;
-            {
-                std::lock_guard<std::mutex> g(mu);
-                if (!err.empty()) return;
-            }
-            std::string e = job(k, t);
-            if (!e.empty()) {
-                std::lock_guard<std::mutex> g(mu);
-                if (err.empty()) err = std::move(e);
-                return;
-            }
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t) th.emplace_back(worker, t);
-    worker(0);
-    for (auto& x : th) x.join();
-    if (!err.empty()) return fail(MI_ERR_INVALID, "%s", err.c_str());
-    return MI_OK;
-}
-
 // ------------------------------------------------------------------------------------------------ reading
 struct TiffInfo {
     uint32_t nx = 0, ny = 0, bits = 0, comp = 1, spp = 1, rps = 0, fmt = 1, predictor = 1, planar = 1, photometric = 1;
@@ -170,21 +143,6 @@ struct TiffInfo {
                off.size() == (size_t)((ny + rps - 1) / rps);
     }
 };
-
-bool pread_all(int fd, void* buf, size_t n, uint64_t at) {
-    char* p = static_cast<char*>(buf);
-    while (n) {
-        const ssize_t r = pread(fd, p, n, (off_t)at);
-        if (r <= 0) {
-            if (r < 0 && errno == EINTR) continue;
-            return false;
-        }
-        p += r;
-        at += (uint64_t)r;
-        n -= (size_t)r;
-    }
-    return true;
-}
 
 // "" or why the file is not a classic little-endian TIFF this reader parses (then *other = true: a TIFF, but for the general reader)
 std::string parse(int fd, TiffInfo& ti, bool* other) {
@@ -251,33 +209,46 @@ struct Fd {
     }
 };
 
+// What a reader does with an open file before it reads a strip: parses it, wants it fast and of the first slice's extents and type,
+// and wants the strips that rows [y0, y1) touch inside the file (raw strips: as long as their rows).  "" or the message.  Both
+// readers, the host's below and the device's (tiff_inflate.hip, through mi::tiff_strips), take and refuse files here.
+std::string checked_strips(int fd, const char* path, int nx, int ny, int dtype, int y0, int y1, TiffInfo& ti) {
+    bool other = false;
+    const std::string e = parse(fd, ti, &other);
+    if (!e.empty()) return std::string(path) + ": " + e;
+    if (!ti.fast()) return std::string(path) + ": not a file this reader decodes (strips of raw or deflate samples, one sample per pixel)";
+    if ((int)ti.nx != nx || (int)ti.ny != ny || ti.dtype() != dtype) return std::string(path) + ": slice shape / type differs from the first slice";
+    const size_t rowb = (size_t)nx * (size_t)(dtype == 4 ? 4 : dtype);
+    struct stat st;
+    if (fstat(fd, &st) != 0) return std::string(path) + ": " + std::strerror(errno);
+    for (uint32_t s = (uint32_t)y0 / ti.rps; s <= (uint32_t)(y1 - 1) / ti.rps; ++s) {
+        if (ti.off[s] > (uint64_t)st.st_size || ti.cnt[s] > (uint64_t)st.st_size - ti.off[s]) return std::string(path) + ": a strip lies outside the file";
+        const uint32_t r0 = s * ti.rps, r1 = std::min<uint32_t>(ti.ny, r0 + ti.rps);
+        if (ti.comp == 1 && ti.cnt[s] < (size_t)(r1 - r0) * rowb) return std::string(path) + ": strip shorter than its rows";
+    }
+    return "";
+}
+
 // rows [y0, y1), columns [x0, x1) of one file into dst (row pitch x1 - x0 samples); "" or the error
 std::string read_slice(const char* path, int nx, int ny, int dtype, int y0, int y1, int x0, int x1, char* dst, Unzip& uz,
                        std::vector<unsigned char>& comp, std::vector<unsigned char>& raw) {
     Fd f(path);
     if (f.fd < 0) return std::string(path) + ": " + std::strerror(errno);
     TiffInfo ti;
-    bool other = false;
-    const std::string e = parse(f.fd, ti, &other);
-    if (!e.empty()) return std::string(path) + ": " + e;
-    if (!ti.fast()) return std::string(path) + ": not a file this reader decodes (strips of raw or deflate samples, one sample per pixel)";
-    if ((int)ti.nx != nx || (int)ti.ny != ny || ti.dtype() != dtype) return std::string(path) + ": slice shape / type differs from the first slice";
+    const std::string e = checked_strips(f.fd, path, nx, ny, dtype, y0, y1, ti);
+    if (!e.empty()) return e;
     const size_t bps = (size_t)(dtype == 4 ? 4 : dtype), rowb = (size_t)nx * bps, outb = (size_t)(x1 - x0) * bps;
-    struct stat st;
-    if (fstat(f.fd, &st) != 0) return std::string(path) + ": " + std::strerror(errno);
     for (uint32_t s = (uint32_t)y0 / ti.rps; s <= (uint32_t)(y1 - 1) / ti.rps; ++s) {
-        if (ti.off[s] > (uint64_t)st.st_size || ti.cnt[s] > (uint64_t)st.st_size - ti.off[s]) return std::string(path) + ": a strip lies outside the file";
         const uint32_t r0 = s * ti.rps, r1 = std::min<uint32_t>(ti.ny, r0 + ti.rps);
         const size_t want = (size_t)(r1 - r0) * rowb;
         const unsigned char* rows = nullptr;
         if (ti.comp == 1) {
-            if (ti.cnt[s] < want) return std::string(path) + ": strip shorter than its rows";
             raw.resize(want);
-            if (!pread_all(f.fd, raw.data(), want, ti.off[s])) return std::string(path) + ": truncated strip";
+            if (!pread_all(f.fd, raw.data(), want, ti.off[s])) return std::string(path) + ": " + mi::kTruncatedStrip;
             rows = raw.data();
         } else {
             comp.resize((size_t)ti.cnt[s]);
-            if (!pread_all(f.fd, comp.data(), comp.size(), ti.off[s])) return std::string(path) + ": truncated strip";
+            if (!pread_all(f.fd, comp.data(), comp.size(), ti.off[s])) return std::string(path) + ": " + mi::kTruncatedStrip;
             raw.resize(want);
             if (!uz.unpack(comp.data(), comp.size(), raw.data(), want)) return std::string(path) + ": a strip does not inflate to its rows";
             rows = raw.data();
@@ -1053,6 +1024,27 @@ struct PinMem {
 };
 
 }  // namespace
+
+// ------------------------------------------------------------------------------------------------ lent to tiff_inflate.hip
+namespace mi {
+
+std::string tiff_strips(const char* path, int nx, int ny, int dtype, int y0, int y1, TiffStrips& out) {
+    Fd f(path);
+    if (f.fd < 0) return std::string(path) + ": " + std::strerror(errno);
+    TiffInfo ti;
+    const std::string e = checked_strips(f.fd, path, nx, ny, dtype, y0, y1, ti);
+    if (!e.empty()) return e;
+    out.rps = ti.rps;
+    out.comp = ti.comp;
+    out.predictor = ti.predictor;
+    out.off = std::move(ti.off);
+    out.cnt = std::move(ti.cnt);
+    return "";
+}
+
+int tiff_thread_count(int asked, int jobs) { return thread_count(asked, jobs); }
+
+}  // namespace mi
 
 extern "C" const char* mi_tiff_codec(void) { return codec().ok ? "libdeflate" : "zlib"; }
 

@@ -183,6 +183,21 @@ class TSVStack(VExtent):
             out[k - k0] = self.read_plane(k)
         return out
 
+    def read_planes_device(self, k0, k1, dev):
+        """``read_planes`` as a device tensor.  With ``MI_TIFF_READ_DEVICE=1`` in the environment (read per call) and files the
+        native TIFF reader decodes, the strips are inflated on the device (``brickio.read_tiff_box_device``); else the planes are
+        read on the host and uploaded.  Only the first file of the range is probed: with the switch on, a later plane that the
+        native reader does not decode, or of another shape or type, raises the device reader's ``capi.MiError`` where
+        ``read_plane`` would have read it through the general reader or raised its ``ValueError``."""
+        import torch
+        if os.environ.get("MI_TIFF_READ_DEVICE") == "1" and k1 > k0:
+            from . import brickio
+            files = self.paths[k0:k1]
+            info = brickio.tiff_info(files[0])
+            if info is not None and info[2] and info[0] == (self.height, self.width) and np.dtype(info[1]) == self.dtype:
+                return brickio.read_tiff_box_device(files, (self.height, self.width), self.dtype, 0, self.height, 0, self.width, device=dev)
+        return torch.from_numpy(self.read_planes(k0, k1)).to(dev)
+
 
 class TSVSimpleVolume:
     """tsv/volume.py:810-860 (a volume from a directory parse): not built."""
@@ -306,7 +321,7 @@ class TSVVolume:
             if not stack.intersects(volume):
                 continue
             zlo, zhi = max(stack.z0, volume.z0), min(stack.z1, volume.z1)
-            planes = torch.from_numpy(stack.read_planes(zlo - stack.z0, zhi - stack.z0)).to(dev)
+            planes = stack.read_planes_device(zlo - stack.z0, zhi - stack.z0, dev)
             held.append(planes)
             ptrs[k] = planes.data_ptr()
         merge_device(dev, self._x0, self._y0, self._z0, self._nz, stacks[0].height, stacks[0].width, ptrs, self._dtype.itemsize,

@@ -1,4 +1,5 @@
-/* TIFF series I/O of the block pipeline (host code, no GPU): the slices decwrap.py reads its boxes from and writes its result to.
+/* TIFF series I/O of the block pipeline: the slices decwrap.py reads its boxes from and writes its result to.  Host code, but for the
+ * two *_device functions: the writer that deflates on the device and the reader that inflates there.
  *
  * Replaces, for the files the pipeline itself meets, LsDeconvolveMultiGPU/load_bl_tif.cpp (a box of a folder of 2-D TIFF slices,
  * one libtiff handle per thread) and save_bl_tif.cpp (one slice per task on all cores, Adobe deflate at ZIPQUALITY 1, predictor 1:
@@ -46,6 +47,21 @@ int mi_tiff_write_series(const char* const* paths, int nz, const void* vol, int 
  * it.  No counterpart in the reference (save_bl_tif.cpp compresses on the host's cores). */
 int mi_tiff_write_series_device(int dev, void* stream, const char* const* paths, int nz, const void* vol, int dtype, int nx, int ny,
                                 int n_threads, int* written);
+
+/* mi_tiff_read_box with `out` in DEVICE memory (n * (y1 - y0) * (x1 - x0) samples on device `dev`): the same files, the same
+ * refusals in the same words -- the host parses the directories exactly as mi_tiff_read_box does -- but the strips the rows touch
+ * cross to the device as they are in the files (pread into pinned memory on n_threads threads, copied in batches of at most 1 GB
+ * of file bytes, 1 GB of inflated rows and 16384 strips) and are decoded there: k_strip_inflate inflates one zlib stream per wave (csrc/tiff_inflate_dev.h: a complete RFC 1950 / 1951
+ * inflater -- stored, fixed and dynamic blocks, any number of them, distances up to 32768, Adler-32 verified; bytes after the
+ * trailer are ignored), k_strip_unpredict_crop undoes predictor 2 and copies the box's rows and columns (strips that are not
+ * compressed take it alone).  A strip that does not inflate to its rows gives MI_ERR_INVALID; the message names the file, the strip
+ * and the decoder's status (header, block type, stored length, over-subscribed / incomplete code, no end-of-block code, invalid
+ * symbol, distance before the start, input exhausted, output size, checksum); what `out` holds is then unspecified.  No input makes
+ * the decoder read past a strip's bytes, write past its rows or run on.  Enqueues on `stream` and synchronises it.  The pinned and
+ * device scratch is kept per device between calls, sized by the largest batch seen; mi_release_cached_memory gives it back.
+ * No counterpart in the reference (load_bl_tif.cpp inflates on the host's cores). */
+int mi_tiff_read_box_device(int dev, void* stream, const char* const* paths, int n, int nx, int ny, int dtype, int y0, int y1, int x0,
+                            int x1, void* out /* device */, int n_threads);
 
 /* one strip (n bytes, rows of rowb bytes, samples of bps bytes) as the device writer codes it, computed on the host by the same rule:
  * pred 0 / 1 (horizontal differencing), runs 0 (literal-only) / 1 (the shorter of the two forms); the whole zlib stream goes to out.
