@@ -150,6 +150,13 @@ class CompositeChannel(C.Structure):
                 ("dy", C.c_int), ("dx", C.c_int), ("reserved", C.c_int)]
 
 
+class Tiff3dJob(C.Structure):
+    """mi_tiff3d_job (include/mi_tiff3d.h): pages [p0, p1) x rows [y0, y1) x columns [x0, x1) of a block file land at (oz, oy, ox) of the box."""
+    _fields_ = [("path", C.c_char_p)] + [(name, C.c_int) for name in ("p0", "p1", "y0", "y1", "x0", "x1", "oz", "oy", "ox")]
+
+
+LZW_OK, LZW_CODE, LZW_FIRST, LZW_INPUT, LZW_OUTPUT, LZW_OLD_STYLE, LZW_TABLE = range(7)   # mi_lzw_status (include/mi_tiff3d.h)
+
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _ip = C.POINTER(C.c_int)
 
@@ -247,6 +254,11 @@ SIGNATURES = {
                                     _i]),
     "mi_tiff_deflate_strip_host": (_i, [_vp, C.c_size_t, _i, C.c_size_t, _i, _i, _vp, C.c_size_t, C.POINTER(C.c_size_t), _ip]),
     "mi_tiff_lzw_encode": (_i, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    # mi_tiff3d.h
+    "mi_tiff3d_info": (_i, [C.c_char_p] + [_ip] * 7),
+    "mi_tiff_lzw_decode": (_i, [_vp, C.c_int64, _vp, C.c_int64, _ip]),
+    "mi_tiff3d_read_box": (_i, [C.POINTER(Tiff3dJob), _i, _i, _i, _i, _i, _vp, _i]),
+    "mi_tiff3d_read_box_device": (_i, [_i, _vp, C.POINTER(Tiff3dJob), _i, _i, _i, _i, _i, _vp, _i]),
     # mi_pystripe.h
     "mi_pystripe_plan_create": (_i, [_i, _i, _i, _i, C.POINTER(PystripeParams), C.POINTER(_vp)]),
     "mi_pystripe_plan_create_wavelet": (_i, [_i, _i, _i, _i, C.POINTER(PystripeParams), C.POINTER(C.c_double), _i, C.POINTER(_vp)]),

@@ -141,5 +141,7 @@ struct PinnedBuf {
 void ncc_drop_cached_slots(int dev);
 // tiff_inflate.hip: gives up the pinned and device scratch the device TIFF reader keeps between calls (dev < 0: of every device)
 void tiff_inflate_drop_scratch(int dev);
+// tiff3d_read.hip: the same for the scratch of the device reader of the tree's block files
+void tiff3d_read_drop_scratch(int dev);
 
 }  // namespace mi
