@@ -7,6 +7,8 @@
   inspect                  a plain-Python inflater that reports what a stream contains (block types, code lengths, distances ...)
   corpus()                 the valid streams, each with the bytes it stands for
   malformed()              the short, fixed list of streams an inflater must refuse, each with the status expected
+  seam_corpus(),           valid streams made for the seams of the device context (pending window, staged input, Adler sums), and the
+  pending_trace            replay of its flush rule over a stream's tokens
 """
 import ctypes as C
 import functools
@@ -187,13 +189,20 @@ def inspect(stream):
     """What a zlib stream contains, from a plain-Python inflater: a dict with ``data`` (the bytes), ``block_types`` (a list),
     ``max_code_length`` (of the literal / length and distance codes in use or declared), ``max_dist_symbol``, ``max_distance``,
     ``len3``, ``len258``, ``len258_dist1``, ``matches``, ``matches_dist1``, ``cl_symbols`` (which of 16 / 17 / 18 occur),
-    ``dist_codes`` (per dynamic block: the lengths of the distance codes declared) and ``empty_stored`` (stored blocks of no bytes)."""
+    ``dist_codes`` (per dynamic block: the lengths of the distance codes declared), ``empty_stored`` (stored blocks of no bytes),
+    ``tokens`` (in order: (1, 0) per literal or stored byte, (length, distance) per match) and ``codes_across`` (the byte offsets,
+    multiples of 1024, that lie strictly inside a literal / length or distance code)."""
     data = bytes(stream)
     src = data + b"\0" * 8
     pos = 16
     out = bytearray()
     info = dict(block_types=[], max_code_length=0, max_dist_symbol=-1, max_distance=0, len3=0, len258=0, len258_dist1=0, matches=0,
-                matches_dist1=0, cl_symbols=set(), dist_codes=[], empty_stored=0)
+                matches_dist1=0, cl_symbols=set(), dist_codes=[], empty_stored=0, tokens=[], codes_across=set())
+    tokens = info["tokens"]
+
+    def across(start, n):
+        if n and start // 8192 != (start + n - 1) // 8192:
+            info["codes_across"].add((start + n - 1) // 8192 * 1024)
     assert data[0] & 15 == 8 and (data[0] << 8 | data[1]) % 31 == 0 and not data[1] & 32
 
     def peek(n):
@@ -214,6 +223,7 @@ def inspect(stream):
             pos += 16
             assert n ^ 0xffff == nn
             out += src[pos >> 3:(pos >> 3) + n]
+            tokens += [(1, 0)] * n
             pos += 8 * n
             info["empty_stored"] += n == 0
             continue
@@ -257,10 +267,12 @@ def inspect(stream):
         while True:
             e = ltab[peek(lmax)]
             assert e
+            across(pos, e & 15)
             pos += e & 15
             s = e >> 4
             if s < 256:
                 out.append(s)
+                tokens.append((1, 0))
                 continue
             if s == 256:
                 break
@@ -268,11 +280,13 @@ def inspect(stream):
             pos += _LEN_EXTRA[s - 257]
             e = dtab[peek(dmax)]
             assert e
+            across(pos, e & 15)
             pos += e & 15
             ds = e >> 4
             d = _DIST_BASE[ds] + peek(_DIST_EXTRA[ds])
             pos += _DIST_EXTRA[ds]
             assert d <= len(out)
+            tokens.append((length, d))
             info["matches"] += 1
             info["matches_dist1"] += d == 1
             info["len3"] += length == 3
@@ -422,3 +436,134 @@ def malformed():
     bad[1] ^= 1
     m.append(("bad_fcheck", bytes(bad), len(img), HEADER))
     return m
+
+
+# ------------------------------------------------------------------------------------------------ the seam streams
+# Streams aimed at the device context of csrc/tiff_inflate.hip (its pending window of PEND bytes in LDS, its input staged STAGE bytes
+# at a time, its Adler sums); tests/test_tiff_seam_streams_host.py asserts what each one claims through inspect() and pending_trace().
+PEND, STAGE = 4096, 1024
+
+
+def pending_trace(tokens):
+    """The flush rule of the device context replayed over inspect()'s tokens: the output waits until PEND bytes or more are pending
+    after a token, then all of it goes out.  [(pos, flushed, npend, length, distance)] per match, as they stand before the match,
+    and [flushed after each flush]."""
+    flushed = npend = 0
+    matches, flushes = [], []
+    for length, dist in tokens:
+        if dist:
+            matches.append((flushed + npend, flushed, npend, length, dist))
+        npend += length
+        if npend >= PEND:
+            flushed += npend
+            npend = 0
+            flushes.append(flushed)
+    return matches, flushes
+
+
+class FixedBlock:
+    """one final block in the fixed code behind a zlib header, the bytes it stands for, and the bytes pending by the flush rule"""
+
+    def __init__(self, seed):
+        self.bw = BitWriter().bits(0x78, 8).bits(0x01, 8).bits(1, 1).bits(1, 2)
+        self.data = bytearray()
+        self.rng = np.random.default_rng(seed)
+        self.npend = 0
+
+    def _token(self, length):
+        self.npend += length
+        if self.npend >= PEND:
+            self.npend = 0
+
+    def literals(self, n):
+        for b in self.rng.integers(0, 256, n, dtype=np.uint8).tolist():
+            self.bw.code(*fixed_code(b))
+            self.data.append(b)
+            self._token(1)
+        return self
+
+    def match(self, length, dist):
+        ls = max(k for k in range(29) if _LEN_BASE[k] <= length) if length < 258 else 28
+        ds = max(k for k in range(30) if _DIST_BASE[k] <= dist)
+        assert 3 <= length <= 258 and 1 <= dist <= len(self.data) and length - _LEN_BASE[ls] < 1 << _LEN_EXTRA[ls]
+        self.bw.code(*fixed_code(257 + ls)).bits(length - _LEN_BASE[ls], _LEN_EXTRA[ls])
+        self.bw.code(ds, 5).bits(dist - _DIST_BASE[ds], _DIST_EXTRA[ds])
+        for _ in range(length):
+            self.data.append(self.data[-dist])
+        self._token(length)
+        return self
+
+    def done(self):
+        self.bw.code(*fixed_code(256))
+        data = bytes(self.data)
+        return self.bw.done() + adler_bytes(data), data
+
+
+def pend_offset_stream(r):
+    """PEND - 1 literals and a match that leaves ``flushed % 4 == r`` at the first flush; PEND - 1 literals and 258 bytes at distance
+    1 (they end at the last byte the pending window can hold when r is 3); 200 literals and 258 bytes whose source begins 100 bytes
+    before ``flushed`` and ends 158 after it; a match at distance npend (its source begins at ``flushed``) and one at npend + 1"""
+    f = FixedBlock(40 + r)
+    f.literals(PEND - 1).match({0: 5, 1: 6, 2: 7, 3: 4}[r], 1000)
+    f.literals(PEND - 1).match(258, 1)
+    f.literals(200).match(258, 300)
+    f.match(20, f.npend).match(20, f.npend + 1)
+    return f.done()
+
+
+OVERLAP_DISTANCES = (1, 2, 3, 63, 64, 65)
+
+
+def overlap_stream():
+    """per distance d: literals up to a few bytes below PEND pending, 258 bytes at distance d (the match crosses PEND and the flush
+    follows it), one literal, and 258 bytes at distance d again: for d > 1 that source begins before ``flushed`` and repeats"""
+    f = FixedBlock(50)
+    for i, d in enumerate(OVERLAP_DISTANCES):
+        f.literals(PEND - 2 - 41 * i - f.npend)
+        f.match(258, d).literals(1).match(258, d)
+    return f.done()
+
+
+def stored_stream(n):
+    """(stream of n bytes in all, bytes): one stored block of n - 11 random bytes"""
+    data = np.random.default_rng(n).integers(0, 256, n - 11, dtype=np.uint8).tobytes()
+    bw = BitWriter().bits(0x78, 8).bits(0x01, 8).bits(1, 1).bits(0, 2).align().bits(len(data), 16).bits(len(data) ^ 0xffff, 16).raw(data)
+    stream = bw.done() + adler_bytes(data)
+    assert len(stream) == n
+    return stream, data
+
+
+def dynamic_edge_stream():
+    """(stream, bytes): one dynamic block of Huffman codes only, its payload the shortest of a fixed sequence for which a code lies
+    across byte STAGE of the stream (found by trial: which payload does it depends on the zlib at hand; the claim is asserted)"""
+    rng = np.random.default_rng(21)
+    pool = (rng.gamma(2.0, 9.0, 6000) % 256).astype(np.uint8).tobytes()
+    for n in range(3000, 3200):
+        stream = _deflate(pool[:n], 9, zlib.Z_HUFFMAN_ONLY)
+        info = inspect(stream)
+        if info["block_types"] == [2] and STAGE in info["codes_across"] and len(stream) > STAGE + 16:
+            return stream, pool[:n]
+    raise AssertionError("no payload puts a code across byte %d" % STAGE)
+
+
+STAGE_EDGE_SIZES = tuple(range(1021, 1029)) + tuple(range(2047, 2051))
+ADLER_TAIL_SIZES = (1, 2, 3, 5, 4099)
+ADLER_BIG = 3 << 19          # 1.5 MiB
+
+
+@functools.lru_cache(maxsize=None)
+def seam_corpus():
+    """{name: (stream, bytes)}: the streams for the seams of the device context"""
+    c = {}
+    for r in range(4):
+        c[f"pend_offset_{r}"] = pend_offset_stream(r)
+    c["overlap_across_flush"] = overlap_stream()
+    for n in STAGE_EDGE_SIZES:
+        c[f"stage_edge_{n}"] = stored_stream(n)
+    c["stage_edge_dyn"] = dynamic_edge_stream()
+    for n in ADLER_TAIL_SIZES:
+        data = np.random.default_rng(100 + n).integers(0, 256, n, dtype=np.uint8).tobytes()
+        c[f"adler_tail_{n}"] = (_deflate(data, 1), data)
+    big = b"\xff" * ADLER_BIG
+    c["adler_big"] = (_deflate(big, 1), big)
+    return c

@@ -1,7 +1,8 @@
 """TIFF LZW in plain Python for the tests of the tree reader: a decoder written from the TIFF 6.0 text (section 13: a table of
 strings, codes of 9 to 12 bits read from the high bit down, ClearCode 256, EndOfInformation 257, the width grows one code early),
 an encoder with the schedule of libtiff's LZWEncode (with switches that make the streams a test needs: no leading Clear, no EOI,
-never a Clear again), an inspector of a stream, the corpus of the host and device tests, and a small reader of TIFF directories.
+never a Clear again), an inspector of a stream, the corpus of the host and device tests, the strips made for the device reader's
+three strip classes and strips of a chosen compressed length (seam_corpus, sized_strip), and a small reader of TIFF directories.
 Nothing here looks at csrc/tiff_lzw_dev.h: the decoder keeps strings, not offsets."""
 import struct
 
@@ -76,8 +77,11 @@ def encode(data, clear_first=True, eoi=True, never_clear=False):
 
 def inspect(stream, want):
     """Decodes `want` bytes from the stream as TIFF 6.0 describes it; {"data", "widths" (set), "clears" (after the first code),
-    "leading_clear", "eoi" (EOI is the next code once the bytes are out), "max_string", "codes", "rest" (whole bytes never looked at)}"""
-    bits = int.from_bytes(stream, "big") if stream else 0
+    "leading_clear", "eoi" (EOI is the next code once the bytes are out), "max_string", "codes", "rest" (whole bytes never looked at),
+    "max_used_offset" (an entry's string begins where the code before it was emitted: the largest such output offset among the table
+    codes the stream uses, -1 without any), "far_long_codes" (table codes in use whose entry begins above offset 65535 and is longer
+    than 64 bytes), "full_tables" (Clears that came when entry 4092, the last before the encoders' Clear, was in the table)}"""
+    padded = bytes(stream) + b"\0\0\0"
     total = 8 * len(stream)
     at = 0
 
@@ -85,7 +89,7 @@ def inspect(stream, want):
         nonlocal at
         if at + width > total:
             raise ValueError("input exhausted")
-        v = (bits >> (total - at - width)) & ((1 << width) - 1)
+        v = (int.from_bytes(padded[at >> 3:(at >> 3) + 3], "big") >> (24 - (at & 7) - width)) & ((1 << width) - 1)
         at += width
         return v
 
@@ -94,8 +98,10 @@ def inspect(stream, want):
 
     table, free, width = fresh()
     out = bytearray()
-    info = {"widths": set(), "clears": 0, "leading_clear": False, "max_string": 0, "codes": 0}
-    old = None
+    info = {"widths": set(), "clears": 0, "leading_clear": False, "max_string": 0, "codes": 0, "max_used_offset": -1, "far_long_codes": 0,
+            "full_tables": 0}
+    begins = {}      # table code -> the output offset its string was defined at
+    old = old_at = None
     first = True
     while len(out) < want:
         code = nxt(width)
@@ -108,6 +114,7 @@ def inspect(stream, want):
                 info["leading_clear"] = True
             else:
                 info["clears"] += 1
+            info["full_tables"] += free >= 4093
             table, free, width = fresh()
             old = None
             first = False
@@ -120,6 +127,9 @@ def inspect(stream, want):
         else:
             if code in table:
                 s = table[code]
+                if code > EOI:
+                    info["max_used_offset"] = max(info["max_used_offset"], begins[code])
+                    info["far_long_codes"] += begins[code] > 65535 and len(s) > 64
             elif code == free:
                 s = table[old] + table[old][:1]
             else:
@@ -127,11 +137,13 @@ def inspect(stream, want):
             if free > 4093:
                 raise ValueError("table overflow")
             table[free] = table[old] + s[:1]
+            begins[free] = old_at
             free += 1
             if free + 1 >= (1 << width) and width < 12:   # "as soon as 511 is stored": the next code has ten bits
                 width += 1
         if len(out) + len(s) > want:
             raise ValueError("output passes the rows")
+        old_at = len(out)
         out += s
         info["max_string"] = max(info["max_string"], len(s))
         old = code
@@ -169,6 +181,54 @@ def corpus():
     c["bytes_after_eoi"] = (encode(text) + b"\x00\xff\x55\xaa\x13", text)
     _CORPUS = c
     return c
+
+
+_SEAMS = None
+
+
+def seam_corpus():
+    """name -> (stream, raw bytes): strips for the three classes of the device reader (rows of at most 16 384 bytes in LDS, rows in
+    global memory with 16-bit offsets up to 65 536 bytes, 32-bit offsets above); tests/test_tiff_seam_streams_host.py asserts what
+    each one holds.  far_strings: after 66 000 bytes of noise a period of 3 bytes, so that strings grow by a byte every third code."""
+    global _SEAMS
+    if _SEAMS is None:
+        datas = {"noise_40000": _noise(40000, 11), "noise_65536": _noise(65536, 12), "noise_70001": _noise(70001, 13),
+                 "far_strings": _noise(66000, 14) + b"\x11\x5a\xe7" * 4000}
+        _SEAMS = {k: (encode(d), d) for k, d in datas.items()}
+    return _SEAMS
+
+
+def sized_strip(width, target, seed):
+    """(strip of exactly `target` bytes, its `width` raw bytes, bytes after EOI): noise trimmed until the encoder gives that length,
+    then one byte (or a period of 2 to 4 bytes) repeated to the row's end.  Not every length is the encoder's: behind Clear and 254
+    codes of 9 bits a strip has 2295 + 10 k bits, and no k puts that into (8 * 512, 8 * 513] -- such a length is the strip of one
+    byte less with one byte after EOI, which a reader does not look at (the corpus' bytes_after_eoi)."""
+    noise = _noise(width, seed)
+    for after in (0, 1):
+        for period in (1, 2, 3, 4):
+            got = _sized(noise, width, target - after, bytes(b ^ 0x80 for b in noise[:period]))
+            if got:
+                return got[0] + b"\xa5" * after, got[1], after
+    raise ValueError(f"no strip of {target} bytes")
+
+
+def _sized(noise, width, target, fill):
+    def make(m):
+        data = noise[:m] + (fill * width)[:width - m]
+        return encode(data), data
+
+    lo, hi = 1, width       # the length grows with the noise, nearly steadily: bisect, then look around
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if len(make(mid)[0]) < target:
+            lo = mid + 1
+        else:
+            hi = mid
+    for m in range(max(1, lo - 4), min(width, lo + 4) + 1):
+        stream, data = make(m)
+        if len(stream) == target:
+            return stream, data
+    return None
 
 
 def malformed():

@@ -127,3 +127,29 @@ def strip_tiff(path, stream, width, rows=1, compression=5):
     with open(path, "wb") as f:
         f.write(b"II*\0" + struct.pack("<I", 8 + len(body)) + body + ifd)
     return str(path)
+
+
+def multi_strip_tiff(path, streams, width, rows_each, compression=5, gap_bytes=0):
+    """A classic one-page TIFF of len(streams) * rows_each x `width` bytes whose strips are `streams`, taken as they are and laid out
+    back to back from file offset 8, strip k behind gap_bytes[k] bytes (a number: the same gap everywhere) that belong to no strip
+    and are not zero.  Strips so begin at any byte; the directory is put on an even offset behind them."""
+    n = len(streams)
+    gaps = [gap_bytes] * n if isinstance(gap_bytes, int) else list(gap_bytes)
+    assert len(gaps) == n
+    body, offs = bytearray(), []
+    for g, s in zip(gaps, streams):
+        body += b"\xa5" * g
+        offs.append(8 + len(body))
+        body += s
+    body += b"\xa5" * (len(body) % 2)
+    cnts = [len(s) for s in streams]
+    at = 8 + len(body)
+    if n > 1:
+        body += struct.pack(f"<{n}I", *offs) + struct.pack(f"<{n}I", *cnts)
+    tags = [(254, 4, 1, 2), (256, 4, 1, width), (257, 4, 1, n * rows_each), (258, 3, 1, 8), (259, 3, 1, compression), (262, 3, 1, 1),
+            (273, 4, n, at if n > 1 else offs[0]), (277, 3, 1, 1), (278, 4, 1, rows_each), (279, 4, n, at + 4 * n if n > 1 else cnts[0]),
+            (284, 3, 1, 1)]
+    ifd = struct.pack("<H", len(tags)) + b"".join(struct.pack("<HHII", *t) for t in tags) + struct.pack("<I", 0)
+    with open(path, "wb") as f:
+        f.write(b"II*\0" + struct.pack("<I", 8 + len(body)) + body + ifd)
+    return str(path)
