@@ -12,7 +12,6 @@
 #include <atomic>
 #include <cerrno>
 #include <cstdint>
-#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -21,8 +20,14 @@
 
 #include "mi_internal.h"
 #include "mi_pyramid.h"
+#include "tiffio_internal.h"
 
 namespace {
+
+using mi::pread_all;
+using mi::put16;
+using mi::put32;
+using mi::put64;
 
 // ------------------------------------------------------------------------------------------------------------------ LZW (TIFF)
 // The encoder of libtiff's tif_lzw.c restated: 9..12-bit codes, MSB first, Clear (256) first, EOI (257) last, code width grown when
@@ -118,15 +123,6 @@ int64_t lzw_encode(LzwTable& T, const uint8_t* src, int64_t n, uint8_t* dst, int
     return bw.overflow ? -1 : bw.n;
 }
 
-int pool_threads(int n_threads) {
-    if (n_threads > 0) return n_threads;
-    if (const char* e = std::getenv("OMP_NUM_THREADS")) {
-        const int v = std::atoi(e);
-        if (v > 0) return v;
-    }
-    return 16;   // never the machine's core count: a GPU host shares its cores between jobs
-}
-
 template <class F>
 void parallel_for(int64_t n, int threads, F f) {
     const int nt = (int)std::min<int64_t>(threads, n);
@@ -157,14 +153,6 @@ struct Block {
     int64_t strip0;       // index of its first strip in the task list
 };
 
-void put16(std::vector<uint8_t>& b, uint16_t v) { b.push_back(v & 0xff); b.push_back(v >> 8); }
-void put32(std::vector<uint8_t>& b, uint32_t v) { for (int i = 0; i < 4; ++i) b.push_back((v >> (8 * i)) & 0xff); }
-void put64(std::vector<uint8_t>& b, uint64_t v) { for (int i = 0; i < 8; ++i) b.push_back((v >> (8 * i)) & 0xff); }
-
-bool pread_all(int fd, void* buf, size_t n, off_t off) {
-    return pread(fd, buf, n, off) == (ssize_t)n;
-}
-
 // offset of the next-IFD field of the last IFD of a file this writer made (walks the chain)
 int last_ifd_link(int fd, bool big, const std::string& path, int expect_pages, uint64_t* link) {
     uint64_t off = 0;
@@ -172,21 +160,21 @@ int last_ifd_link(int fd, bool big, const std::string& path, int expect_pages, u
     int pages = 0;
     for (;;) {
         if (big) {
-            if (!pread_all(fd, &off, 8, (off_t)pos)) return mi::fail(MI_ERR_INVALID, "%s: truncated TIFF", path.c_str());
+            if (!pread_all(fd, &off, 8, pos)) return mi::fail(MI_ERR_INVALID, "%s: truncated TIFF", path.c_str());
         } else {
             uint32_t o32;
-            if (!pread_all(fd, &o32, 4, (off_t)pos)) return mi::fail(MI_ERR_INVALID, "%s: truncated TIFF", path.c_str());
+            if (!pread_all(fd, &o32, 4, pos)) return mi::fail(MI_ERR_INVALID, "%s: truncated TIFF", path.c_str());
             off = o32;
         }
         if (off == 0) break;
         ++pages;
         if (big) {
             uint64_t cnt;
-            if (!pread_all(fd, &cnt, 8, (off_t)off)) return mi::fail(MI_ERR_INVALID, "%s: truncated IFD", path.c_str());
+            if (!pread_all(fd, &cnt, 8, off)) return mi::fail(MI_ERR_INVALID, "%s: truncated IFD", path.c_str());
             pos = off + 8 + cnt * 20;
         } else {
             uint16_t cnt;
-            if (!pread_all(fd, &cnt, 2, (off_t)off)) return mi::fail(MI_ERR_INVALID, "%s: truncated IFD", path.c_str());
+            if (!pread_all(fd, &cnt, 2, off)) return mi::fail(MI_ERR_INVALID, "%s: truncated IFD", path.c_str());
             pos = off + 2 + (uint64_t)cnt * 12;
         }
     }
@@ -369,7 +357,7 @@ extern "C" int mi_tiff3d_write_blocks(int n, const char* const* paths, const voi
         B.strip0 = nstrips;
         nstrips += (int64_t)B.pages * ((B.h + rows_per_strip - 1) / rows_per_strip);
     }
-    const int threads = pool_threads(n_threads);
+    const int threads = mi::tree_pool_threads(n_threads);
     // 1) every strip of every page of every block, encoded in parallel
     std::vector<Strip> strips(nstrips);
     std::vector<std::unique_ptr<LzwTable>> tables(threads);

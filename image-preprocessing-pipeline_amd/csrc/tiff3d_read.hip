@@ -362,15 +362,6 @@ std::string parse_file(const char* path, File3D& f) {
     return std::string();
 }
 
-int pool_threads(int n_threads) {
-    if (n_threads > 0) return n_threads;
-    if (const char* e = std::getenv("OMP_NUM_THREADS")) {
-        const int v = std::atoi(e);
-        if (v > 0) return v;
-    }
-    return 16;   // never the machine's core count: a GPU host shares its cores between jobs
-}
-
 // ------------------------------------------------------------------------------------------------------------------ the plan of a call
 // a run: strips [s0, s1) of a page that are read with one pread (they follow each other in the file)
 struct Run {
@@ -431,7 +422,7 @@ int make_plan(const char* who, const mi_tiff3d_job* jobs, int n_jobs, int box_z,
     const int nf = (int)paths.size();
     P.files.resize((size_t)nf);
     for (auto& f : P.files) f.reset(new File3D());
-    MI_TRY(mi::run_jobs(nf, std::max(1, std::min(pool_threads(n_threads), nf)), [&](int k, int) { return parse_file(paths[(size_t)k], *P.files[(size_t)k]); }));
+    MI_TRY(mi::run_jobs(nf, std::max(1, std::min(mi::tree_pool_threads(n_threads), nf)), [&](int k, int) { return parse_file(paths[(size_t)k], *P.files[(size_t)k]); }));
     for (int j = 0; j < n_jobs; ++j) {
         const mi_tiff3d_job& J = jobs[j];
         const File3D& f = *P.files[(size_t)P.job_file[(size_t)j]];
@@ -455,22 +446,9 @@ std::string strip_error(const File3D& f, uint32_t page, uint32_t strip, int stat
 }
 
 // ------------------------------------------------------------------------------------------------------------------ device scratch
-size_t slot(size_t n) { return (n + 15) & ~(size_t)15; }
+using mi::slot;
 
-struct Scratch {
-    std::mutex mu;
-    mi::PinnedBuf h_bytes, h_jobs;
-    mi::DevBuf d_bytes, d_jobs;
-};
-std::mutex g_mu;
-std::map<int, std::shared_ptr<Scratch>>& scratches() {
-    static auto* m = new std::map<int, std::shared_ptr<Scratch>>;   // (never destroyed: the runtime may be gone by then)
-    return *m;
-}
-int grow(mi::DevBuf& b, size_t n) {
-    if (n <= b.bytes) return MI_OK;
-    return b.alloc(n + n / 8);
-}
+mi::ScratchPool g_scratch;   // this reader's own
 
 size_t lzw_lds_bytes(bool lds_rows, bool wide, uint32_t entries, uint32_t max_rows) {
     return 4 * ((size_t)kStageWords + 1 + entries + (wide ? (entries + 1) / 2 : 0)) + (lds_rows ? (size_t)((max_rows + 3) & ~3u) : 0);
@@ -487,14 +465,7 @@ void launch_place(hipStream_t s, uint32_t max_rows, uint32_t njobs, const unsign
 }  // namespace
 
 namespace mi {
-void tiff3d_read_drop_scratch(int dev) {
-    std::lock_guard<std::mutex> g(g_mu);
-    auto& m = scratches();
-    for (auto it = m.begin(); it != m.end();) {
-        if (dev < 0 || it->first == dev) it = m.erase(it);   // (a call in flight keeps its scratch until it returns)
-        else ++it;
-    }
-}
+void tiff3d_read_drop_scratch(int dev) { g_scratch.drop(dev); }
 }  // namespace mi
 
 extern "C" int mi_tiff3d_info(const char* path, int* nx, int* ny, int* pages, int* dtype, int* compression, int* rows_per_strip, int* bigtiff) {
@@ -533,7 +504,7 @@ extern "C" int mi_tiff3d_read_box(const mi_tiff3d_job* jobs, int n_jobs, int box
     MI_REQUIRE(P.pieces.size() < 0x7fffffffull, "mi_tiff3d_read_box: more than 2^31 pages in the box");
     const int np = (int)P.pieces.size();
     if (np == 0) return MI_OK;
-    const int nt = std::max(1, std::min(pool_threads(n_threads), np));
+    const int nt = std::max(1, std::min(mi::tree_pool_threads(n_threads), np));
     struct Work {
         std::vector<unsigned char> file, rows;
         std::vector<uint32_t> off;
@@ -588,13 +559,7 @@ extern "C" int mi_tiff3d_read_box_device(int dev, void* stream, const mi_tiff3d_
     if (P.pieces.empty()) return MI_OK;
     hipStream_t s = mi::as_stream(stream);
 
-    std::shared_ptr<Scratch> sc;
-    {
-        std::lock_guard<std::mutex> g(g_mu);
-        std::shared_ptr<Scratch>& e = scratches()[dev];
-        if (!e) e = std::make_shared<Scratch>();
-        sc = e;
-    }
+    const std::shared_ptr<mi::DeviceScratch> sc = g_scratch.get(dev);
     std::lock_guard<std::mutex> hold(sc->mu);
 
     // Batches of whole pieces (a page of a job), bounded as the slice reader bounds its batches: at most 1 GB of file bytes and 1 GB
@@ -678,12 +643,11 @@ extern "C" int mi_tiff3d_read_box_device(int dev, void* stream, const mi_tiff3d_
         }
         const size_t n_lzw = lj[0].size() + lj[1].size() + lj[2].size();
         // [LzwJob x n_lzw | PlaceJob x | status x n_lzw], the same layout on both sides
-        const size_t place_at = slot(n_lzw * sizeof(LzwJob)), status_at = place_at + slot(pj.size() * sizeof(PlaceJob));
-        const size_t jobs_bytes = status_at + slot(n_lzw * sizeof(int32_t));
+        const auto [place_at, status_at, jobs_bytes] = mi::job_layout(n_lzw, sizeof(LzwJob), pj.size(), sizeof(PlaceJob), n_lzw, sizeof(int32_t));
         MI_TRY(sc->h_bytes.reserve(read_bytes));
         MI_TRY(sc->h_jobs.reserve(jobs_bytes));
-        MI_TRY(grow(sc->d_bytes, read_bytes + row_bytes));
-        MI_TRY(grow(sc->d_jobs, jobs_bytes));
+        MI_TRY(sc->grow(sc->d_bytes, read_bytes + row_bytes));
+        MI_TRY(sc->grow(sc->d_jobs, jobs_bytes));
         unsigned char* hb = sc->h_bytes.as<unsigned char>();
         unsigned char* hj = sc->h_jobs.as<unsigned char>();
         int32_t* status = reinterpret_cast<int32_t*>(hj + status_at);
@@ -698,7 +662,7 @@ extern "C" int mi_tiff3d_read_box_device(int dev, void* stream, const mi_tiff3d_
         }
         // 3) the strips' bytes into pinned memory (the bytes between a run's end and the next multiple of 16 stay as they are: the
         //    kernel masks what is not the strip's)
-        MI_TRY(mi::run_jobs((int)reads.size(), std::max(1, std::min<int>(pool_threads(n_threads), (int)reads.size())), [&](int i, int) -> std::string {
+        MI_TRY(mi::run_jobs((int)reads.size(), std::max(1, std::min<int>(mi::tree_pool_threads(n_threads), (int)reads.size())), [&](int i, int) -> std::string {
             const RunAt& ra = reads[(size_t)i];
             const File3D& f = *P.files[(size_t)P.pieces[b0 + ra.piece].file];
             return mi::pread_all(f.fd, hb + ra.at, (size_t)ra.r.len, ra.r.off) ? std::string() : f.path + ": " + mi::kTruncatedStrip;

@@ -1,4 +1,4 @@
-// The device TIFF reader (include/mi_tiffio.h, mi_tiff_read_box_device): the mirror of the device writer in tiffio.hip.  The host
+// The device TIFF reader (include/mi_tiffio.h, mi_tiff_read_box_device): the mirror of the device writer in tiff_deflate.hip.  The host
 // parses the directories and reads the compressed strips into pinned memory; the bytes cross to the device as they are in the files,
 // and two kernels make the box there:
 //   k_strip_inflate         one zlib stream per wave (a work-group is one wave).  The decoder is the text of tiff_inflate_dev.h: every
@@ -21,13 +21,10 @@
 //     written by flush(), which ends in __syncthreads() -- a work-group release / acquire of global memory -- before `flushed` moves.
 // LDS per wave: sizeof(InflateLds) = 9 340 bytes (tables 3 956, staged input 1 024, pending output 4 360): 17 waves per CU by LDS
 // (160 KiB), 20 by registers (83 VGPRs: 5 waves per SIMD); a box of 64 slices of 8 strips is 512 waves, two per CU.
-#include <fcntl.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <cerrno>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <vector>
@@ -214,24 +211,9 @@ __global__ __launch_bounds__(256) void k_strip_unpredict_crop(const unsigned cha
 }
 
 // ------------------------------------------------------------------------------------------------ host
-size_t slot(size_t n) { return (n + 15) & ~(size_t)15; }
+using mi::slot;
 
-// The scratch of a device: pinned and device memory sized by the largest batch seen, kept between calls and given back by
-// mi_release_cached_memory.  A call holds `mu` from its first batch to its last.
-struct Scratch {
-    std::mutex mu;
-    mi::PinnedBuf h_bytes, h_jobs;
-    mi::DevBuf d_bytes, d_jobs;
-};
-std::mutex g_mu;
-std::map<int, std::shared_ptr<Scratch>>& scratches() {
-    static auto* m = new std::map<int, std::shared_ptr<Scratch>>;   // (never destroyed: the runtime may be gone by then)
-    return *m;
-}
-int grow(mi::DevBuf& b, size_t n) {
-    if (n <= b.bytes) return MI_OK;
-    return b.alloc(n + n / 8);
-}
+mi::ScratchPool g_scratch;   // this reader's own
 
 struct Strip {
     int file;
@@ -250,14 +232,7 @@ void launch_crop(hipStream_t s, uint32_t max_rows, uint32_t njobs, const unsigne
 }  // namespace
 
 namespace mi {
-void tiff_inflate_drop_scratch(int dev) {
-    std::lock_guard<std::mutex> g(g_mu);
-    auto& m = scratches();
-    for (auto it = m.begin(); it != m.end();) {
-        if (dev < 0 || it->first == dev) it = m.erase(it);   // (a call in flight keeps its scratch until it returns)
-        else ++it;
-    }
-}
+void tiff_inflate_drop_scratch(int dev) { g_scratch.drop(dev); }
 }  // namespace mi
 
 extern "C" int mi_tiff_read_box_device(int dev, void* stream, const char* const* paths, int n, int nx, int ny, int dtype, int y0, int y1, int x0, int x1,
@@ -273,7 +248,7 @@ extern "C" int mi_tiff_read_box_device(int dev, void* stream, const char* const*
 
     // the directories, a file per task: the host reader's checks and words
     std::vector<mi::TiffStrips> dirs((size_t)n);
-    MI_TRY(mi::run_jobs(n, mi::tiff_thread_count(n_threads, n), [&](int k, int) { return mi::tiff_strips(paths[k], nx, ny, dtype, y0, y1, dirs[(size_t)k]); }));
+    MI_TRY(mi::run_jobs(n, mi::series_threads(n_threads, n), [&](int k, int) { return mi::tiff_strips(paths[k], nx, ny, dtype, y0, y1, dirs[(size_t)k]); }));
     std::vector<Strip> strips;
     for (int k = 0; k < n; ++k) {
         const mi::TiffStrips& d = dirs[(size_t)k];
@@ -296,13 +271,7 @@ extern "C" int mi_tiff_read_box_device(int dev, void* stream, const char* const*
     }
     MI_REQUIRE((uint64_t)n * (uint64_t)(y1 - y0) < 0xffffffffull, "mi_tiff_read_box_device: more than 2^32 rows in the box");
 
-    std::shared_ptr<Scratch> sc;
-    {
-        std::lock_guard<std::mutex> g(g_mu);
-        std::shared_ptr<Scratch>& e = scratches()[dev];
-        if (!e) e = std::make_shared<Scratch>();
-        sc = e;
-    }
+    const std::shared_ptr<mi::DeviceScratch> sc = g_scratch.get(dev);
     std::lock_guard<std::mutex> hold(sc->mu);
 
     // batches of bounded size: at most 1 GB of file bytes, 1 GB of inflated rows and 16384 strips at a time.  A stream is a wave and
@@ -324,12 +293,11 @@ extern "C" int mi_tiff_read_box_device(int dev, void* stream, const char* const*
         }
         const size_t nb = b1 - b0;
         // the jobs: [StripJob x n_packed | CropJob x nb | status x n_packed], the same layout on both sides
-        const size_t crop_at = slot(n_packed * sizeof(StripJob)), status_at = crop_at + slot(nb * sizeof(CropJob));
-        const size_t jobs_bytes = status_at + slot(n_packed * sizeof(int32_t));
+        const auto [crop_at, status_at, jobs_bytes] = mi::job_layout(n_packed, sizeof(StripJob), nb, sizeof(CropJob), n_packed, sizeof(int32_t));
         MI_TRY(sc->h_bytes.reserve(read_bytes));
         MI_TRY(sc->h_jobs.reserve(jobs_bytes));
-        MI_TRY(grow(sc->d_bytes, read_bytes + row_bytes));   // the file's bytes, then the inflated rows
-        MI_TRY(grow(sc->d_jobs, jobs_bytes));
+        MI_TRY(sc->grow(sc->d_bytes, read_bytes + row_bytes));   // the file's bytes, then the inflated rows
+        MI_TRY(sc->grow(sc->d_jobs, jobs_bytes));
         unsigned char* hb = sc->h_bytes.as<unsigned char>();
         StripJob* sj = reinterpret_cast<StripJob*>(sc->h_jobs.as<unsigned char>());
         CropJob* cj = reinterpret_cast<CropJob*>(sc->h_jobs.as<unsigned char>() + crop_at);
@@ -356,14 +324,12 @@ extern "C" int mi_tiff_read_box_device(int dev, void* stream, const char* const*
             }
             ra += slot(st.read);
         }
-        MI_TRY(mi::run_jobs((int)nb, mi::tiff_thread_count(n_threads, (int)nb), [&](int i, int) -> std::string {
+        MI_TRY(mi::run_jobs((int)nb, mi::series_threads(n_threads, (int)nb), [&](int i, int) -> std::string {
             const Strip& st = strips[b0 + (size_t)i];
             const char* path = paths[st.file];
-            const int fd = open(path, O_RDONLY | O_CLOEXEC);
-            if (fd < 0) return std::string(path) + ": " + std::strerror(errno);
-            const bool ok = mi::pread_all(fd, hb + read_at[(size_t)i], st.read, st.off);
-            close(fd);
-            return ok ? std::string() : std::string(path) + ": " + mi::kTruncatedStrip;
+            mi::Fd f(path);
+            if (f.fd < 0) return std::string(path) + ": " + std::strerror(errno);
+            return mi::pread_all(f.fd, hb + read_at[(size_t)i], st.read, st.off) ? std::string() : std::string(path) + ": " + mi::kTruncatedStrip;
         }));
         unsigned char* d_all = sc->d_bytes.as<unsigned char>();
         unsigned char* dj = sc->d_jobs.as<unsigned char>();

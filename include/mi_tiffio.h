@@ -39,7 +39,7 @@ int mi_tiff_write_series(const char* const* paths, int nz, const void* vol, int 
                          int n_threads, int* written);
 
 /* The same files from a volume that lies in DEVICE memory (vol [nz][ny][nx] on device `dev`), deflated there: every strip is one
- * dynamic-Huffman block (csrc/tiffio.hip: counting kernels, codes built on the host, encode kernel), the host only frames the streams
+ * dynamic-Huffman block (csrc/tiff_deflate.hip: counting kernels, codes built on the host, encode kernel), the host only frames the streams
  * and writes the files.  The only string matching is that of runs: a strip is coded either with every byte a literal, or -- when that
  * is shorter, as on the zero background of a stitched or clipped volume -- with its runs of equal bytes as matches at distance 1
  * (zlib's Z_RLE; the token rule is in DESIGN.md, "TIFF on the device").  MI_TIFF_DEVICE_RUNS=0 in the environment (read per call)

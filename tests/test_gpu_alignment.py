@@ -608,7 +608,7 @@ def test_merge_slab_into_an_offset_box(dev, g, dtype, off, blending):
 
 @pytest.mark.parametrize("off", INT_OFFS[np.uint16])
 def test_device_tiff_writer_reads_an_offset_volume(dev, g, tmp_path, off):
-    """tiffio.hip, strip_bytes: 16-byte loads when the strip starts on a 16-byte boundary, else byte by byte."""
+    """tiff_deflate.hip, strip_bytes: 16-byte loads when the strip starts on a 16-byte boundary, else byte by byte."""
     from ipp_amd import brickio
     vol = (np.cumsum(np.random.default_rng(11).standard_normal((3, 17, 32)), axis=2) * 30 + 20000).clip(0, 65535).astype(np.uint16)
     assert brickio.save_tiff_series_device(tmp_path / "d", g.like(vol, off)) == 3

@@ -116,3 +116,32 @@ def test_device_writer_on_many_small_shapes(dev, tmp_path):
         back = np.stack([np.asarray(Image.open(f)).reshape(ny, nx) for f in files])
         assert back.dtype == v.dtype and np.array_equal(back, v), (case, v.shape, dt)
         assert np.array_equal(brickio.load_tiff_series(d), v), (case, v.shape, dt)
+
+
+def _layout_generator():
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location(
+        "make_tiff_layout_golden", os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_tiff_layout_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    return gen
+
+
+@pytest.mark.parametrize("name", ["u8_2x64x96", "u16_2x64x96", "u16_2x600x1000"])
+def test_device_writer_files_are_byte_identical(dev, tmp_path, name):
+    """Every byte of the device writer's files (tiff_deflate.hip; their tail is mi::finish_file of tiffio.hip) against the SHA-256 sums
+    recorded on an MI355X before the writer moved to a unit of its own and the slice writers' tails became one
+    (tests/golden/make_tiff_layout_golden.py --device).  The device's Huffman code is the project's own and deterministic, so the sums
+    hold on every host.  The larger case has two strips per slice, a smooth slice (predictor 2: tag 317) and a noise slice (no tag 317)."""
+    import json
+    gen = _layout_generator()
+    with open(gen.GOLDEN) as f:
+        golden = json.load(f)
+    assert "device" in golden and name in golden["device"], "run tests/golden/make_tiff_layout_golden.py --device on the GPU"
+    paths = gen.write_device(name, tmp_path / "d")
+    dirs = [gen.directory(p) for p in paths]
+    assert all(d[273][1] == gen.DEVICE_CASES[name][2] and d[259][2] == 8 for d in dirs)
+    if name == "u16_2x600x1000":
+        assert dirs[0][317][2] == 2 and 317 not in dirs[1]
+    assert [gen.sha(p) for p in paths] == golden["device"][name]
