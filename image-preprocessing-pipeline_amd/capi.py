@@ -254,6 +254,13 @@ SIGNATURES = {
                                     _i]),
     "mi_tiff_deflate_strip_host": (_i, [_vp, C.c_size_t, _i, C.c_size_t, _i, _i, _vp, C.c_size_t, C.POINTER(C.c_size_t), _ip]),
     "mi_tiff_lzw_encode": (_i, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    "mi_tiff_lzw_encode_strips_device": (_i, [_i, _vp, C.c_int64, C.POINTER(_vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                              C.POINTER(C.c_int64), C.POINTER(C.c_int64), _vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64),
+                                              C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "mi_tiff3d_write_blocks_device": (_i, [_i, _vp, _i, C.POINTER(C.c_char_p), C.POINTER(_vp), C.POINTER(C.c_int64), _ip, _ip, _ip, _i, _i, _i,
+                                           _i, _i]),
+    "mi_tiff3d_write_blocks_encoded": (_i, [_i, C.POINTER(C.c_char_p), _ip, _ip, _ip, _i, _i, _i, C.POINTER(_vp), C.POINTER(C.c_int64), _i]),
+    "mi_tiff_lzw_encode_device_batches": (C.c_int64, []),
     # mi_tiff3d.h
     "mi_tiff3d_info": (_i, [C.c_char_p] + [_ip] * 7),
     "mi_tiff_lzw_decode": (_i, [_vp, C.c_int64, _vp, C.c_int64, _ip]),

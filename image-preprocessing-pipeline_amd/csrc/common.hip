@@ -142,6 +142,7 @@ extern "C" size_t mi_release_cached_memory(int dev) {
     mi::ncc_drop_cached_slots(dev);  // their buffers go back to the pool first
     mi::tiff_inflate_drop_scratch(dev);
     mi::tiff3d_read_drop_scratch(dev);
+    mi::tiff3d_lzw_enc_drop_scratch(dev);
     mi::Pool& P = mi::pool();
     std::lock_guard<std::mutex> g(P.mu);
     return P.trim(dev);

@@ -143,5 +143,6 @@ void ncc_drop_cached_slots(int dev);
 void tiff_inflate_drop_scratch(int dev);
 // tiff3d_read.hip: the same for the scratch of the device reader of the tree's block files
 void tiff3d_read_drop_scratch(int dev);
+void tiff3d_lzw_enc_drop_scratch(int dev);
 
 }  // namespace mi

@@ -140,18 +140,8 @@ void parallel_for(int64_t n, int threads, F f) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------ TIFF pages
-struct Strip {
-    std::vector<uint8_t> data;
-    bool ok = true;
-};
-
-struct Block {
-    std::string path;
-    const uint8_t* first;
-    int64_t sp, sr;       // page / row strides in samples
-    int w, h, pages, page0, total;
-    int64_t strip0;       // index of its first strip in the task list
-};
+using Block = mi::Tiff3dBlock;
+using mi::StripRef;
 
 // offset of the next-IFD field of the last IFD of a file this writer made (walks the chain)
 int last_ifd_link(int fd, bool big, const std::string& path, int expect_pages, uint64_t* link) {
@@ -233,7 +223,7 @@ size_t add_ifd(std::vector<uint8_t>& buf, uint64_t base, bool big, int w, int h,
     return link;
 }
 
-int write_block(const Block& B, const std::vector<Strip>& strips, int bytes, int comp, int rps, int force_big) {
+int write_block(const Block& B, const StripRef* strips, int bytes, int comp, int rps, int force_big) {
     const int nstrip_page = (B.h + rps - 1) / rps;
     int fd;
     bool big;
@@ -276,11 +266,11 @@ int write_block(const Block& B, const std::vector<Strip>& strips, int bytes, int
     size_t prev_link_idx = 0;
     for (int p = 0; p < B.pages; ++p) {
         for (int s = 0; s < nstrip_page; ++s) {
-            const Strip& S = strips[B.strip0 + (int64_t)p * nstrip_page + s];
+            const StripRef& S = strips[B.strip0 + (int64_t)p * nstrip_page + s];
             if (buf.size() % 2) buf.push_back(0);
             offs[s] = end + buf.size();
-            counts[s] = S.data.size();
-            buf.insert(buf.end(), S.data.begin(), S.data.end());
+            counts[s] = S.n;
+            buf.insert(buf.end(), S.p, S.p + S.n);
         }
         if (buf.size() % 2) buf.push_back(0);
         const size_t at = buf.size();
@@ -321,6 +311,50 @@ int write_block(const Block& B, const std::vector<Strip>& strips, int bytes, int
 
 }  // namespace
 
+namespace mi {
+
+int tiff3d_parse_blocks(const char* who, int n, const char* const* paths, const void* const* first, const int64_t* strides, const int* dims,
+                        const int* page0, const int* page_total, int bytes, int rows_per_strip, std::vector<Tiff3dBlock>& blocks, int64_t* n_strips) {
+    blocks.assign((size_t)n, Block());
+    int64_t nstrips = 0;
+    for (int b = 0; b < n; ++b) {
+        Block& B = blocks[b];
+        MI_REQUIRE(paths[b] && (!first || first[b]), "%s: block %d has no path or samples", who, b);
+        B.path = paths[b];
+        B.first = first ? static_cast<const uint8_t*>(first[b]) : nullptr;
+        B.sp = strides[2 * b];
+        B.sr = strides[2 * b + 1];
+        B.w = dims[3 * b];
+        B.h = dims[3 * b + 1];
+        B.pages = dims[3 * b + 2];
+        B.page0 = page0[b];
+        B.total = page_total[b];
+        MI_REQUIRE(B.w > 0 && B.h > 0 && B.pages >= 0 && B.page0 >= 0, "%s: block %d of %d x %d x %d from page %d", who, b,
+                   B.w, B.h, B.pages, B.page0);
+        MI_REQUIRE((int64_t)rows_per_strip * B.w * bytes <= 0xffffffffll, "%s: a strip of block %d passes 4 GiB", who, b);
+        B.strip0 = nstrips;
+        nstrips += (int64_t)B.pages * ((B.h + rows_per_strip - 1) / rows_per_strip);
+    }
+    *n_strips = nstrips;
+    return MI_OK;
+}
+
+int tiff3d_write_files(const std::vector<Tiff3dBlock>& blocks, const StripRef* strips, int bytes, int compression, int rows_per_strip, int bigtiff,
+                       int threads) {
+    const int n = (int)blocks.size();
+    std::vector<int> rc(n, MI_OK);
+    std::vector<std::string> msg(n);
+    parallel_for(n, threads, [&](int64_t b, int) {
+        rc[b] = write_block(blocks[b], strips, bytes, compression, rows_per_strip, bigtiff);
+        if (rc[b] != MI_OK) msg[b] = mi::last_error_ref();
+    });
+    for (int b = 0; b < n; ++b)
+        if (rc[b] != MI_OK) return mi::fail(rc[b], "%s", msg[b].c_str());
+    return MI_OK;
+}
+
+}  // namespace mi
+
 extern "C" int mi_tiff_lzw_encode(const void* src, int64_t n, void* dst, int64_t cap, int64_t* written) {
     MI_REQUIRE((src || n == 0) && dst && written && n >= 0, "mi_tiff_lzw_encode: bad arguments");
     std::unique_ptr<LzwTable> T(new LzwTable());
@@ -337,28 +371,14 @@ extern "C" int mi_tiff3d_write_blocks(int n, const char* const* paths, const voi
     MI_REQUIRE(bytes == 1 || bytes == 2, "mi_tiff3d_write_blocks: %d bytes per sample (1 or 2)", bytes);
     MI_REQUIRE(compression == 0 || compression == 1, "mi_tiff3d_write_blocks: compression %d (0 none, 1 LZW)", compression);
     MI_REQUIRE(rows_per_strip >= 1, "mi_tiff3d_write_blocks: %d rows per strip", rows_per_strip);
-    std::vector<Block> blocks(n);
+    std::vector<Block> blocks;
     int64_t nstrips = 0;
-    for (int b = 0; b < n; ++b) {
-        Block& B = blocks[b];
-        MI_REQUIRE(paths[b] && first[b], "mi_tiff3d_write_blocks: block %d has no path or samples", b);
-        B.path = paths[b];
-        B.first = static_cast<const uint8_t*>(first[b]);
-        B.sp = strides[2 * b];
-        B.sr = strides[2 * b + 1];
-        B.w = dims[3 * b];
-        B.h = dims[3 * b + 1];
-        B.pages = dims[3 * b + 2];
-        B.page0 = page0[b];
-        B.total = page_total[b];
-        MI_REQUIRE(B.w > 0 && B.h > 0 && B.pages >= 0 && B.page0 >= 0, "mi_tiff3d_write_blocks: block %d of %d x %d x %d from page %d", b,
-                   B.w, B.h, B.pages, B.page0);
-        MI_REQUIRE((int64_t)rows_per_strip * B.w * bytes <= 0xffffffffll, "mi_tiff3d_write_blocks: a strip of block %d passes 4 GiB", b);
-        B.strip0 = nstrips;
-        nstrips += (int64_t)B.pages * ((B.h + rows_per_strip - 1) / rows_per_strip);
-    }
+    MI_TRY(mi::tiff3d_parse_blocks("mi_tiff3d_write_blocks", n, paths, first, strides, dims, page0, page_total, bytes, rows_per_strip, blocks, &nstrips));
     const int threads = mi::tree_pool_threads(n_threads);
     // 1) every strip of every page of every block, encoded in parallel
+    struct Strip {
+        std::vector<uint8_t> data;
+    };
     std::vector<Strip> strips(nstrips);
     std::vector<std::unique_ptr<LzwTable>> tables(threads);
     std::vector<std::vector<uint8_t>> rowbuf(threads);
@@ -385,18 +405,30 @@ extern "C" int mi_tiff3d_write_blocks(int n, const char* const* paths, const voi
         if (!tables[t]) tables[t].reset(new LzwTable());
         S.data.resize((size_t)(raw.size() * 3 / 2 + 16));
         const int64_t m = lzw_encode(*tables[t], raw.data(), (int64_t)raw.size(), S.data.data(), (int64_t)S.data.size());
-        if (m < 0) { fail_nomem = 1; S.ok = false; return; }
+        if (m < 0) { fail_nomem = 1; return; }
         S.data.resize((size_t)m);
     });
     if (fail_nomem) return mi::fail(MI_ERR_NOMEM, "mi_tiff3d_write_blocks: LZW output larger than its bound");
     // 2) each file gets its pages appended
-    std::vector<int> rc(n, MI_OK);
-    std::vector<std::string> msg(n);
-    parallel_for(n, threads, [&](int64_t b, int) {
-        rc[b] = write_block(blocks[b], strips, bytes, compression, rows_per_strip, bigtiff);
-        if (rc[b] != MI_OK) msg[b] = mi::last_error_ref();
-    });
-    for (int b = 0; b < n; ++b)
-        if (rc[b] != MI_OK) return mi::fail(rc[b], "%s", msg[b].c_str());
-    return MI_OK;
+    std::vector<StripRef> refs(nstrips);
+    for (int64_t k = 0; k < nstrips; ++k) refs[k] = {strips[k].data.data(), strips[k].data.size()};
+    return mi::tiff3d_write_files(blocks, refs.data(), bytes, compression, rows_per_strip, bigtiff, threads);
+}
+
+extern "C" int mi_tiff3d_write_blocks_encoded(int n, const char* const* paths, const int* dims, const int* page0, const int* page_total, int bytes,
+                                              int rows_per_strip, int bigtiff, const void* const* strips, const int64_t* lengths, int n_threads) {
+    MI_REQUIRE(n >= 0 && (n == 0 || (paths && dims && page0 && page_total && strips && lengths)), "mi_tiff3d_write_blocks_encoded: null pointer");
+    MI_REQUIRE(bytes == 1 || bytes == 2, "mi_tiff3d_write_blocks_encoded: %d bytes per sample (1 or 2)", bytes);
+    MI_REQUIRE(rows_per_strip >= 1, "mi_tiff3d_write_blocks_encoded: %d rows per strip", rows_per_strip);
+    std::vector<int64_t> strides(2 * (size_t)n, 0);
+    std::vector<Block> blocks;
+    int64_t nstrips = 0;
+    MI_TRY(mi::tiff3d_parse_blocks("mi_tiff3d_write_blocks_encoded", n, paths, nullptr, strides.data(), dims, page0, page_total, bytes, rows_per_strip,
+                                   blocks, &nstrips));
+    std::vector<StripRef> refs(nstrips);
+    for (int64_t k = 0; k < nstrips; ++k) {
+        MI_REQUIRE(strips[k] && lengths[k] > 0, "mi_tiff3d_write_blocks_encoded: strip %lld has no bytes", (long long)k);
+        refs[k] = {static_cast<const uint8_t*>(strips[k]), (size_t)lengths[k]};
+    }
+    return mi::tiff3d_write_files(blocks, refs.data(), bytes, 1, rows_per_strip, bigtiff, mi::tree_pool_threads(n_threads));
 }

@@ -144,6 +144,29 @@ std::string tiff_strips(const char* path, int nx, int ny, int dtype, int y0, int
 // what every reader says after the path when a strip that lies inside the file cannot be read whole
 constexpr const char* kTruncatedStrip = "truncated strip";
 
+// ------------------------------------------------------------------------------------------------ the tree's block files
+// What the host writer (tiff3d.hip) and the device route (tiff3d_lzw_enc.hip) share: the block walk and the page and directory
+// assembly.  Both routes hand the same function their strips, so the files differ only where the streams do.
+struct StripRef {
+    const unsigned char* p;   // the strip as it goes into the file (encoded or raw)
+    size_t n;
+};
+
+struct Tiff3dBlock {
+    std::string path;
+    const uint8_t* first;   // sample (0, 0, 0) of the block; host or device memory, the route knows which
+    int64_t sp, sr;         // page / row strides in samples
+    int w, h, pages, page0, total;
+    int64_t strip0;         // index of its first strip in the list of all strips: (block, page, strip) order
+};
+
+// the arguments of mi_tiff3d_write_blocks checked and turned into blocks (first may be NULL: no samples, the strips are given); `who` begins the messages
+int tiff3d_parse_blocks(const char* who, int n, const char* const* paths, const void* const* first, const int64_t* strides, const int* dims,
+                        const int* page0, const int* page_total, int bytes, int rows_per_strip, std::vector<Tiff3dBlock>& blocks, int64_t* n_strips);
+// every block gets its pages appended, files in parallel on `threads` threads; strips[B.strip0 + page * strips per page + strip]
+int tiff3d_write_files(const std::vector<Tiff3dBlock>& blocks, const StripRef* strips, int bytes, int compression, int rows_per_strip, int bigtiff,
+                       int threads);
+
 // ------------------------------------------------------------------------------------------------ the device readers
 // parts of a buffer begin at multiples of 16 bytes
 inline size_t slot(size_t n) { return (n + 15) & ~(size_t)15; }

@@ -7,7 +7,7 @@
 Takes the reference's flag spelling (TemplateCLI.cpp) for this subset: -s/--src, -d/--dst, --sfmt, --dfmt, --resolutions,
 --halve=mean|max, --clist=0, --height/--width/--depth, --isotropic, --fixed_tiling, --libtiff_uncompress, --libtiff_rowsperstrip,
 --libtiff_bigtiff, --V0/--V1/--H0/--H1/--D0/--D1, --noprogressbar (and --mdata_fname, which the reference ignores for this
-destination).  Other source / destination formats, a --clist other than 0 and multi-channel slices are refused by name.
+destination).  Of its own: --slab_rows (rows of a device band) and --lzw_encoder=host|device (where the LZW strips are encoded).  Other source / destination formats, a --clist other than 0 and multi-channel slices are refused by name.
 """
 import argparse
 import os
@@ -42,6 +42,8 @@ def parser():
     p.add_argument("--noprogressbar", action="store_true")
     p.add_argument("--mdata_fname", default="")
     p.add_argument("--slab_rows", type=int, default=None, help="rows of a device band (default: from the free device memory)")
+    p.add_argument("--lzw_encoder", choices=("host", "device"), default=None,
+                   help="where the LZW strips are encoded (default: MI_TERAFLY_WRITE_DEVICE, else the host)")
     return p
 
 
@@ -86,7 +88,8 @@ def main(argv=None):
     try:
         p = terafly.convert(a.src, a.dst, a.resolutions, a.halve, (a.height, a.width, a.depth), a.isotropic, a.fixed_tiling,
                             (a.V0, a.V1, a.H0, a.H1, a.D0, a.D1), not a.libtiff_uncompress, a.libtiff_rowsperstrip,
-                            a.libtiff_bigtiff, slab_rows=a.slab_rows, progress=None if a.noprogressbar else progress)
+                            a.libtiff_bigtiff, slab_rows=a.slab_rows, progress=None if a.noprogressbar else progress,
+                            encoder=a.lzw_encoder)
     except ValueError as e:
         print(f"teraconverter.py: {e}", file=sys.stderr)
         return 2

@@ -13,7 +13,9 @@ on its own (``mi_pyramid_slab``, include/mi_pyramid.h), so a group loses its odd
 RES(...x9) of 37 slices holds 8 pages.  The level names still say ``depth / 2^h``.  A group's slices go to the device in row
 bands sized from the free device memory (band heights are multiples of 2^deepest level, so the bands halve as the whole plane
 does); each level's pages are appended to their block files (``mi_tiff3d_write_blocks``, LZW on a host thread pool) as soon as
-the group is done, as appendSlice2Tiff3DFile does.
+the group is done, as appendSlice2Tiff3DFile does.  With ``encoder="device"`` the strips are encoded on the GPU from the band's
+levels instead (``mi_tiff_lzw_encode_strips_device``; only the streams come back) and the pages appended from the collected
+streams (``mi_tiff3d_write_blocks_encoded``): the same files, byte for byte.
 """
 from __future__ import annotations
 
@@ -310,15 +312,92 @@ def _band_rows(p: Plan, nbytes, device, slab_rows=None):
     return max(unit, (int(slab_rows) // unit) * unit)
 
 
+ENCODERS = ("host", "device")
+DEFAULT_ENCODER = "host"         # what an unset MI_TERAFLY_WRITE_DEVICE means (DESIGN section 23 holds the measurement that decides it)
+route_counts = {"host": 0, "device": 0}   # conversions per route in this process: the route report of the tests
+
+
+def _encoder_route(encoder, compression, rows_per_strip, one_band):
+    """"host" or "device" for a conversion.  ``encoder`` "host" / "device" is taken at its word (and "device" refused where the
+    device route does not go); None reads MI_TERAFLY_WRITE_DEVICE (1: device, 0: host, unset: DEFAULT_ENCODER) and quietly takes the
+    host route where the device route does not go."""
+    if encoder is not None and encoder not in ENCODERS:
+        raise ValueError(f"encoder={encoder!r}: host or device")
+    why = None
+    if not compression:
+        why = "the device route writes LZW strips: an uncompressed tree (--libtiff_uncompress) is written on the host"
+    elif rows_per_strip > 1 and not one_band:
+        why = (f"strips of {rows_per_strip} rows may cross the row bands of the device: the device route takes them only when one "
+               "band covers the whole height (a larger --slab_rows, or --libtiff_rowsperstrip=1)")
+    if encoder == "device" and why:
+        raise ValueError(f"encoder=device: {why}")
+    if encoder is None:
+        env = os.environ.get("MI_TERAFLY_WRITE_DEVICE", "")
+        if env not in ("", "0", "1"):
+            raise ValueError(f"MI_TERAFLY_WRITE_DEVICE={env}: 0 (host) or 1 (device)")
+        encoder = {"": DEFAULT_ENCODER, "0": "host", "1": "device"}[env]
+    return "host" if why else encoder
+
+
+def _encode_band(lib, capi, dev, entries, levels, rps, bytes_, strip_ptr, strip_len, keep):
+    """The strips of the group's blocks that lie in one row band, encoded from the band's device tensors.  ``entries``:
+    [(level, first group page, pages, block row0, block rows, block col0, block cols, first strip)]; ``levels[i]`` = (tensor of
+    level i for the band, its first row in the level).  The streams' addresses and lengths go to strip_ptr / strip_len at the
+    strips' places in (block, page, strip) order; ``keep`` holds the buffers they point into."""
+    src, rows, gidx, rowb, stride = [], [], [], [], []
+    for i, g0, n, r0b, nr, c0, nc, strip0 in entries:
+        t, a = levels[i]
+        hb, W = t.shape[1], t.shape[2]
+        spp = (nr + rps - 1) // rps
+        s_lo = max(0, (a - r0b + rps - 1) // rps)
+        s_hi = min(spp, (a + hb - r0b + rps - 1) // rps)
+        if s_hi <= s_lo or n <= 0:
+            continue
+        s_idx = np.arange(s_lo, s_hi, dtype=np.int64)
+        pp = np.arange(n, dtype=np.int64)[:, None]
+        y = r0b + s_idx * rps - a                           # the strip's first row in the band's tensor
+        src.append((np.uint64(t.data_ptr()) + (((g0 + pp) * hb + y[None, :]) * W + c0).astype(np.uint64) * np.uint64(bytes_)).ravel())
+        gidx.append((strip0 + pp * spp + s_idx[None, :]).ravel())
+        rows.append(np.broadcast_to(np.minimum(rps, nr - s_idx * rps)[None, :], (n, s_idx.size)).ravel())
+        rowb.append(np.full(n * s_idx.size, nc * bytes_, np.int32))
+        stride.append(np.full(n * s_idx.size, W * bytes_, np.int64))
+    if not src:
+        return
+    src = np.ascontiguousarray(np.concatenate(src), np.uint64)
+    gidx = np.concatenate(gidx)
+    rows = np.ascontiguousarray(np.concatenate(rows), np.int32)
+    rowb = np.concatenate(rowb)
+    stride = np.concatenate(stride)
+    m = src.size
+    raw = rows.astype(np.int64) * rowb
+    out = np.empty(int((raw * 3 // 2 + 16 + 3).sum()), np.uint8)      # every stream at its bound, each from a multiple of 4
+    out_off = np.empty(m, np.int64)
+    lengths = np.empty(m, np.int64)
+    status = np.empty(m, np.int32)
+    used = C.c_int64()
+    i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+    capi.check(lib.mi_tiff_lzw_encode_strips_device(
+        dev.index, capi.current_stream_ptr(dev), m, src.ctypes.data_as(C.POINTER(C.c_void_p)), rows.ctypes.data_as(i32p),
+        rowb.ctypes.data_as(i32p), stride.ctypes.data_as(i64p), None, None, None, 0, out.ctypes.data, out.size,
+        out_off.ctypes.data_as(i64p), lengths.ctypes.data_as(i64p), status.ctypes.data_as(i32p), C.byref(used)))
+    strip_ptr[gidx] = np.uint64(out.ctypes.data) + out_off.astype(np.uint64)
+    strip_len[gidx] = lengths
+    keep.append(out)
+
+
 def convert(src, dst, resolutions="0", halve="mean", block=(-1, -1, -1), isotropic=False, fixed_tiling=False,
             sub=(-1, -1, -1, -1, -1, -1), compression=True, rows_per_strip=1, bigtiff=False, device=None, slab_rows=None,
-            threads=0, progress=None):
+            threads=0, progress=None, encoder=None):
     """Writes the TeraFly tree of the 2-D series in ``src`` under ``dst`` (an existing folder); ``slab_rows`` fixes the rows of
-    a device band (default: from the free device memory).  Returns the Plan."""
+    a device band (default: from the free device memory).  ``encoder``: "host" encodes the LZW strips on a host thread pool,
+    "device" on the GPU from the levels where the pyramid kernel left them (only the streams come back; the files are the same
+    bytes); None takes MI_TERAFLY_WRITE_DEVICE (1 / 0) or, unset, DEFAULT_ENCODER.  Returns the Plan."""
     import torch
     from . import capi
     if halve not in HALVE:
         raise ValueError(f"--halve={halve}: mean or max")
+    if encoder is not None and encoder not in ENCODERS:
+        raise ValueError(f"encoder={encoder!r}: host or device")
     dst = Path(dst)
     if not dst.is_dir():
         raise ValueError(f"destination {dst} is not an existing folder (teraconverter -d must exist)")
@@ -330,6 +409,8 @@ def convert(src, dst, resolutions="0", halve="mean", block=(-1, -1, -1), isotrop
     n_lv = p.n_res - 1
     halve_d = [1 if p.hp[i] == p.hp[i - 1] + 1 else 0 for i in range(1, p.n_res)]
     band = _band_rows(p, p.bytes, dev, slab_rows)
+    route = _encoder_route(encoder, compression, int(rows_per_strip), band >= p.height)
+    route_counts[route] += 1
     for i in range(p.n_res):
         if p.selected[i]:
             for _, _, _, _, dirname in p.blocks(i):
@@ -340,6 +421,12 @@ def convert(src, dst, resolutions="0", halve="mean", block=(-1, -1, -1), isotrop
     all_groups = p.groups()
     for gi, (z, z_size) in enumerate(all_groups):
         if not appends[gi]:
+            continue
+        if route == "device":
+            _device_group(lib, capi, series, p, dst, dev, tdtype, z, z_size, appends[gi], pages_in, band, halve, halve_d,
+                          int(rows_per_strip), bigtiff, threads)
+            if progress:
+                progress(gi + 1, len(all_groups))
             continue
         host = [None] * p.n_res
         host[0] = series.read(p.D0 + z, p.D0 + z + z_size, p.V0, p.V0 + p.height, p.H0, p.H0 + p.width, threads)
@@ -382,6 +469,52 @@ def convert(src, dst, resolutions="0", halve="mean", block=(-1, -1, -1), isotrop
             progress(gi + 1, len(all_groups))
     write_mdata(p, dst)
     return p
+
+
+def _device_group(lib, capi, series, p, dst, dev, tdtype, z, z_size, group, pages_in, band, halve, halve_d, rps, bigtiff, threads):
+    """One z-group on the device route: every row band is uploaded and halved as on the host route, the strips of every selected
+    level that lie in the band are encoded from the device tensors, and after the last band the group's pages are appended to
+    their block files from the collected streams."""
+    import torch
+    n_lv = p.n_res - 1
+    need = [p.selected[k + 1] or (k % 2 == 1 and k + 1 < n_lv) for k in range(n_lv)]
+    level0 = series.read(p.D0 + z, p.D0 + z + z_size, p.V0, p.V0 + p.height, p.H0, p.H0 + p.width, threads)
+    paths, dims, page0, total, entries = [], [], [], [], []
+    nstrips = 0
+    for i, k, g0, n in group:
+        for r0, nr, c0, nc, dirname in p.blocks(i):
+            vh = dirname.split("/")[1]
+            path = str(dst / p.res_dir(i) / dirname / f"{vh}_{p.d_name(i, p.d_block_start(i, k))}.tif")
+            paths.append(os.fsencode(path))
+            dims += [nc, nr, n]
+            page0.append(pages_in.get(path, 0))
+            total.append(p.deps[i][k])
+            pages_in[path] = pages_in.get(path, 0) + n
+            entries.append((i, g0, n, r0, nr, c0, nc, nstrips))
+            nstrips += n * ((nr + rps - 1) // rps)
+    strip_ptr = np.zeros(nstrips, np.uint64)
+    strip_len = np.zeros(nstrips, np.int64)
+    keep = []
+    for r0 in range(0, p.height, band):
+        r1 = min(p.height, r0 + band)
+        slab = torch.from_numpy(level0[:, r0:r1]).to(dev)
+        levels = {0: (slab, r0)}
+        if n_lv > 0:
+            bshapes = level_shapes(slab.shape, n_lv, halve_d)
+            outs = [torch.empty(s, dtype=tdtype, device=dev) if need[k] else None for k, s in enumerate(bshapes)]
+            pyramid_slab(slab, n_lv, halve_d, halve, outs)
+            for k, o in enumerate(outs):
+                if o is not None and p.selected[k + 1] and o.numel():
+                    levels[k + 1] = (o, r0 >> (k + 1))
+        _encode_band(lib, capi, dev, [e for e in entries if e[0] in levels], levels, rps, p.bytes, strip_ptr, strip_len, keep)
+        del slab, levels
+    if nstrips and not strip_len.all():
+        raise RuntimeError("terafly.convert: a strip of the group lies in no row band")
+    m = len(paths)
+    capi.check(lib.mi_tiff3d_write_blocks_encoded(m, (C.c_char_p * m)(*paths), (C.c_int * (3 * m))(*dims), (C.c_int * m)(*page0),
+                                                  (C.c_int * m)(*total), p.bytes, rps, 1 if bigtiff else 0,
+                                                  strip_ptr.ctypes.data_as(C.POINTER(C.c_void_p)), strip_len.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  int(threads)))
 
 
 def write_mdata(p: Plan, dst):

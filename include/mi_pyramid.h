@@ -46,6 +46,40 @@ int mi_tiff3d_write_blocks(int n, const char* const* paths, const void* const* f
  * first and EOI last.  MI_ERR_NOMEM when cap is too small (n * 3 / 2 + 16 always suffices).  Host only. */
 int mi_tiff_lzw_encode(const void* src, int64_t n, void* dst, int64_t cap, int64_t* written);
 
+/* ---- the device route of the tree writer: the LZW strips encoded on the GPU (csrc/tiff3d_lzw_enc.hip), one strip per wave.  The
+ * stream of a strip is the one mi_tiff_lzw_encode writes, byte for byte. */
+
+/* Encodes n strips that lie in device memory.  Strip k: rows[k] rows of row_bytes[k] bytes, row r at (const char*)src[k] +
+ * r * row_stride[k] (any byte address; at most 1 GiB a strip).  The streams return packed in `out` [host, out_cap bytes]: strip
+ * k at out_off[k] with lengths[k] bytes, in strip order, each stream beginning at a multiple of 4 bytes -- the up to 3 bytes
+ * between a stream's end and the next stream's start are 0 and nothing else lies between them; *out_bytes is the end of the last.
+ * status[k] is 0, or 1 when the stream is longer than the strip's slot; lengths[k] then still is the whole stream's length, `out`
+ * holds what fitted, and the call returns MI_ERR_NOMEM after all strips are done.  The slots: with slot_off == NULL (and
+ * slot_cap == NULL, d_slots == NULL) the library's own scratch, each slot rows * row_bytes * 3 / 2 + 16 bytes, which always
+ * suffice.  Otherwise strip k is encoded into bytes [slot_off[k], slot_off[k] + slot_cap[k]) of d_slots [device, d_slots_bytes
+ * bytes, 4-byte aligned; slot_off[k] a multiple of 4]; no other byte of d_slots is written.  Batches of at most 1 GB of rows and
+ * 2^20 strips; synchronises `stream`. */
+int mi_tiff_lzw_encode_strips_device(int dev, void* stream, int64_t n, const void* const* src, const int32_t* rows, const int32_t* row_bytes,
+                                     const int64_t* row_stride, const int64_t* slot_off, const int64_t* slot_cap, void* d_slots,
+                                     int64_t d_slots_bytes, void* out, int64_t out_cap, int64_t* out_off, int64_t* lengths, int32_t* status,
+                                     int64_t* out_bytes);
+
+/* mi_tiff3d_write_blocks with first[b] pointing into device memory: the same block / page / strip walk, the strips encoded on
+ * the device, the same page and directory assembly -- the files equal the host route's byte for byte.  compression must be 1.
+ * A stream longer than its bound is MI_ERR_NOMEM with the host route's message.  Synchronises `stream`. */
+int mi_tiff3d_write_blocks_device(int dev, void* stream, int n, const char* const* paths, const void* const* first, const int64_t* strides,
+                                  const int* dims, const int* page0, const int* page_total, int bytes, int compression, int rows_per_strip,
+                                  int bigtiff, int n_threads);
+
+/* The page and directory assembly alone, for strips that are already LZW streams [host]: the blocks as in mi_tiff3d_write_blocks
+ * (no samples, no strides); strips[] / lengths[] hold every strip in (block, page, strip of the page) order.  What a caller uses
+ * that encoded a block's strips in several mi_tiff_lzw_encode_strips_device calls (row bands).  Host only. */
+int mi_tiff3d_write_blocks_encoded(int n, const char* const* paths, const int* dims, const int* page0, const int* page_total, int bytes,
+                                   int rows_per_strip, int bigtiff, const void* const* strips, const int64_t* lengths, int n_threads);
+
+/* Batches the device encoder has run in this process: the route report of the conversion's tests. */
+int64_t mi_tiff_lzw_encode_device_batches(void);
+
 #ifdef __cplusplus
 }
 #endif
