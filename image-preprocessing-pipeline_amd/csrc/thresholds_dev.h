@@ -1,4 +1,4 @@
-// What thresholds.hip shares with the per-tile clip estimate of pystripe.hip: the device pieces of the 256-bin histogram (keys,
+// What thresholds.hip shares with the per-tile clip estimate of pystripe_clips.hip: the device pieces of the 256-bin histogram (keys,
 // the bin of a sample, the wave-aggregated LDS count) and launchers of the kernels that stay compiled once, in thresholds.hip
 // (range / counter initialisation, the edges of numpy.histogram, the multi-Otsu search).  Launchers enqueue on `s` and check
 // nothing but the launch: the callers have checked their arguments.

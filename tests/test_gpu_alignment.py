@@ -557,7 +557,7 @@ def test_isodown_halving_of_an_offset_stack(dev, g, dtype, off):
 
 @pytest.mark.parametrize("dtype,off", INT_CASES, ids=INT_IDS)
 def test_pystripe_run_on_an_offset_batch(dev, g, dtype, off):
-    """pystripe.hip, uniform_kernel<T, VEC>: tiles of 33 x 64 samples (a multiple of 16 bytes each), one of them uniform."""
+    """pystripe.hip (launch_uniform), uniform_kernel<T, VEC>: tiles of 33 x 64 samples (a multiple of 16 bytes each), one of them uniform."""
     from ipp_amd import pystripe as ps
     tiles = np.stack([PU.synthetic_tile((33, 64), 100 + i, dtype, "rows" if i % 2 else "cols") for i in range(3)])
     tiles[1] = 123
