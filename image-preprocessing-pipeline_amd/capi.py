@@ -24,6 +24,7 @@ PS_U8, PS_U16, PS_F32 = 0, 1, 2   # mi_pystripe_dtype (include/mi_pystripe.h)
 PS_PADDING = {"reflect": 0, "wrap": 1, "symmetric": 2, "edge": 3}   # mi_pystripe_padding
 PS_DOWN = {"max": 0, "min": 1, "mean": 2, "median": 3}   # mi_pystripe_down
 PS_MEDIAN_MAX_BLOCK = 64  # MI_PS_MEDIAN_MAX_BLOCK
+PS_NOTCH_ROUTE = ("pass", "level", "axis", "n", "kp", "kb", "R", "threads", "lds")   # a record of mi_pystripe_plan_notch_routes
 PS_AUTO_MIN, PS_AUTO_MED, PS_AUTO_MAX = 1, 2, 4   # bits of PystripeParams.bleach_auto (MI_PS_AUTO_*)
 PS_CLIPS_UNIFORM, PS_CLIPS_OK, PS_CLIPS_TOO_FEW, PS_CLIPS_ORDER, PS_CLIPS_NONFINITE = -1, 0, 1, 2, 3   # mi_pystripe_clip_status
 CODES_U8, CODES_U16 = 0, 1   # mi_code_dtype (include/mi_thresholds.h)
@@ -272,6 +273,7 @@ SIGNATURES = {
     "mi_pystripe_derive_wavelet": (_i, [_i, _i, _i, C.POINTER(PystripeParams), _i, C.POINTER(PystripeInfo)]),
     "mi_pystripe_plan_destroy": (_i, [_vp]),
     "mi_pystripe_plan_info": (_i, [_vp, C.POINTER(PystripeInfo)]),
+    "mi_pystripe_plan_notch_routes": (_i, [_vp, _ip, _i]),
     "mi_pystripe_derive": (_i, [_i, _i, _i, C.POINTER(PystripeParams), C.POINTER(PystripeInfo)]),
     "mi_pystripe_run": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64]),
     "mi_pystripe_pad_size": (_i, [_i, _i, C.c_double]),

@@ -487,6 +487,21 @@ extern "C" int mi_pystripe_plan_info(void* plan, mi_pystripe_info* info) {
     return MI_OK;
 }
 
+extern "C" int mi_pystripe_plan_notch_routes(void* plan, int* out, int cap) {
+    MI_REQUIRE(plan, "mi_pystripe_plan_notch_routes: null pointer");
+    const Plan& P = *static_cast<Plan*>(plan);
+    const int count = (int)P.tabs.size();
+    MI_REQUIRE(cap >= 0 && (i64)count * MI_PS_NOTCH_ROUTE_INTS <= (i64)cap && (out || count == 0),
+               "mi_pystripe_plan_notch_routes: cap = %d ints, the plan's %d records need %d", cap, count, count * MI_PS_NOTCH_ROUTE_INTS);
+    const int Lv = P.info.levels;
+    for (int i = 0; i < count; ++i) {
+        const NotchTab& t = P.tabs[i];   // build_tables: [pass][level 1..L][axis]
+        const int rec[MI_PS_NOTCH_ROUTE_INTS] = {i / (2 * Lv), (i / 2) % Lv + 1, i % 2, t.n, t.kp, t.kb, t.R, t.threads, (int)t.lds};
+        std::copy(rec, rec + MI_PS_NOTCH_ROUTE_INTS, out + (size_t)i * MI_PS_NOTCH_ROUTE_INTS);
+    }
+    return count;
+}
+
 extern "C" int mi_pystripe_plan_set_log_table(void* plan, const float* table, int ncodes) {
     MI_REQUIRE(plan && table, "mi_pystripe_plan_set_log_table: null pointer");
     Plan& P = *static_cast<Plan*>(plan);

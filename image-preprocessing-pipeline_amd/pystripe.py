@@ -340,6 +340,20 @@ class Plan:
             table = np.ascontiguousarray(log_table(256 if self.in_dtype == np.uint8 else 65536), dtype=np.float32)
             capi.check(capi.lib().mi_pystripe_plan_set_log_table(self._h, table.ctypes.data, table.size))
 
+    def notch_routes(self):
+        """The notch kernel's route per (pass, level, axis) as mi_pystripe_plan_notch_routes reports it, in the plan's order: dicts
+        of capi.PS_NOTCH_ROUTE (``R`` lines per work-group, ``lds`` bytes), and ``lines``, the lines of ``n`` samples the launch
+        covers (the other axis' ``n`` at that level).  Axis 1 is listed also when the plan is not bidirectional."""
+        width = len(capi.PS_NOTCH_ROUTE)
+        buf = (C.c_int * (2 * 2 * capi.PS_MAX_LEVELS * width))()   # two passes, two axes per level
+        count = capi.lib().mi_pystripe_plan_notch_routes(self._h, buf, len(buf))
+        if count < 0:
+            capi.check(count)
+        routes = [dict(zip(capi.PS_NOTCH_ROUTE, buf[i * width:(i + 1) * width])) for i in range(count)]
+        for i, r in enumerate(routes):
+            r["lines"] = routes[i ^ 1]["n"]
+        return routes
+
     def clips(self, n=None):
         """(clips float32 [n, 3], status int32 [n]) of the first ``n`` tiles (default: all) of the last ``run``: the triple
         (min, med, max) in log1p units the bleach correction used -- min raised to log1p(1) -- and capi.PS_CLIPS_*.  The caller has

@@ -137,6 +137,13 @@ int mi_pystripe_plan_create_wavelet(int dev, int ny, int nx, int in_dtype, const
 int mi_pystripe_derive_wavelet(int ny, int nx, int in_dtype, const mi_pystripe_params* params, int taps, mi_pystripe_info* info);
 int mi_pystripe_plan_destroy(void* plan);
 int mi_pystripe_plan_info(void* plan, mi_pystripe_info* info);
+/* The notch kernel's route per (pass, level, axis), for tests and profiles: MI_PS_NOTCH_ROUTE_INTS ints per record into out[cap]
+ * (host memory) -- pass, level (1 = finest), axis (0: cH along axis -1, 1: cV along axis -2), line length n, packed positions with a
+ * non-zero weight kp, bins kb, lines per work-group R, threads, dynamic LDS in bytes -- in the order the plan holds them: pass,
+ * then level, then axis (axis 1 is listed whether or not the plan is bidirectional).  Returns the number of records (0 for a plan
+ * without a stripe filter); MI_ERR_INVALID naming cap when cap ints do not hold them.  Reads the plan only. */
+#define MI_PS_NOTCH_ROUTE_INTS 9
+int mi_pystripe_plan_notch_routes(void* plan, int* out, int cap);
 /* The bookkeeping alone, without a device: what a plan for this shape would derive (scratch_bytes_per_tile included). */
 int mi_pystripe_derive(int ny, int nx, int in_dtype, const mi_pystripe_params* params, mi_pystripe_info* info);
 /* count tiles, dense one after the other in `in` (ny x nx of in_dtype) -> `out` (out_ny x out_nx of out_dtype); flat: ny x nx

@@ -263,9 +263,10 @@ def test_batch_past_2_to_31_samples(ps, dev, max_batch):
 
 
 def test_live_plans_with_different_lds_needs(ps, dev):
-    """The notch kernel's dynamic-LDS limit belongs to the kernel, not to a plan: plans whose finest lines need 66 KB, 50 KB (both above the 48 KB
-    at which the limit has to be raised) and 22 KB of LDS are alive together (as in batch_filter with several tile shapes) and run in turn; every result equals the one
-    the plan gave before the others existed."""
+    """The notch kernel's dynamic-LDS limit belongs to the kernel, not to a plan: plans whose finest lines need 66 176 and 55 872 bytes
+    (both above the 48 KB at which the limit has to be raised) and 28 992 bytes of LDS, as Plan.notch_routes() reports them, are alive
+    together (as in batch_filter with several tile shapes) and run in turn; every result equals the one the plan gave before the
+    others existed.  All three take four lines per work-group; tests/test_gpu_pystripe_notch_routes.py does the same for two and one."""
     import torch
     shapes = [(2048, 2048), (1400, 1400), (300, 300), (1400, 1400), (2048, 2048)]
     kw = dict(sigma=(250, 250), **PIPE)
