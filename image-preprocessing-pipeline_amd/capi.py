@@ -202,6 +202,7 @@ SIGNATURES = {
     "mi_rl_destroy": (_i, [_vp]),
     "mi_rl_engine": (_i, [_vp]),
     "mi_rl_separable": (_i, [_vp]),
+    "mi_rl_sep_route": (_i, [_vp, _i, _ip]),
     "mi_rl_pair_layout": (_i, [_vp]),
     "mi_rl_device_bytes": (_sz, [_vp]),
     "mi_rl_forward_ratio": (_i, [_vp, _vp, _vp, _vp]),

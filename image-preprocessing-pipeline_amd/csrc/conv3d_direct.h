@@ -42,6 +42,14 @@ struct SepTaps {
     int n;
 };
 bool sep3d_fits(int nx, const int* k, const int* offs);
+// what sep3d_launch runs for a convolution that fits: the kernel (acc: k_sep3d_acc<., npre, kzb>, else the LDS-ring kernel
+// k_sep3d<., npre>, kzb 0), the planes of a z chunk and their count, the (x, y) tiles and the dynamic LDS bytes
+struct SepRoute {
+    bool acc;
+    int kzb, npre, zchunk, chunks, tiles_xy;
+    size_t lds;
+};
+SepRoute sep3d_route(int nx, int ny, int nz, const int* k, const int* offs);
 int sep3d_launch(hipStream_t s, const float* in, float* out, int nx, int ny, int nz, const SepTaps taps[3], const int* offs, const int* bnd3,
                  int epi_kind, const ConvEpilogue& epi);
 int gauss3d_async(hipStream_t s, float* vol, float* work, int nx, int ny, int nz, const float* sigma, const int* ksize);

@@ -261,6 +261,19 @@ extern "C" size_t mi_rl_device_bytes(const mi_rl_ctx* ctx) {
 }
 
 extern "C" int mi_rl_separable(const mi_rl_ctx* ctx) { return ctx && ctx->separable ? (ctx->sep_single ? 2 : 1) : 0; }
+extern "C" int mi_rl_sep_route(const mi_rl_ctx* ctx, int adjoint, int* out) {
+    MI_REQUIRE(ctx && out, "mi_rl_sep_route: null pointer");
+    for (int i = 0; i < 6; ++i) out[i] = 0;
+    if (!(ctx->engine == MI_ENGINE_DIRECT && ctx->separable && ctx->sep_single)) return MI_OK;
+    const SepRoute r = sep3d_route(ctx->n[0], ctx->n[1], ctx->n[2], ctx->k, adjoint ? ctx->off_adj : ctx->off_fwd);
+    out[0] = r.acc ? 1 : 2;
+    out[1] = r.kzb;
+    out[2] = r.npre;
+    out[3] = r.zchunk;
+    out[4] = r.chunks;
+    out[5] = (int)r.lds;
+    return MI_OK;
+}
 extern "C" int mi_rl_pair_layout(const mi_rl_ctx* ctx) {
     return ctx && ctx->engine == MI_ENGINE_FFT && ctx->fft && ctx->fft->native && ctx->fft->native->dims.paired ? 1 : 0;
 }

@@ -379,6 +379,24 @@ bool sep3d_fits(int nx, const int* k, const int* c) {
            sep_patch_quads(k, c) <= 6 * SF_THREADS;
 }
 
+// Every decision of a launch in one place (sep3d_launch takes its kernel, grid and LDS size from this; mi_rl_sep_route reports it, so a
+// test can assert the build it means to cover).  Pure host arithmetic.
+SepRoute sep3d_route(int nx, int ny, int nz, const int* k, const int* offs) {
+    SepRoute r{};
+    // chunks along z: long enough that the kz - 1 planes of run-in are a small share, short enough to fill the device
+    r.tiles_xy = ((nx + SF_TX - 1) / SF_TX) * ((ny + SF_TY - 1) / SF_TY);
+    int zchunk = std::max(64, 8 * k[2]);
+    while (zchunk > 2 * k[2] && zchunk > 16 && (size_t)r.tiles_xy * ((nz + zchunk - 1) / zchunk) < 1024) zchunk /= 2;
+    r.zchunk = std::min(zchunk, nz);
+    r.chunks = (nz + r.zchunk - 1) / r.zchunk;
+    r.npre = sep_patch_quads(k, offs) > 3 * SF_THREADS ? 6 : 3;
+    // z window in registers (k_sep3d_acc); MI_SEP_RING=1 (probes build): the LDS-ring kernel
+    r.acc = k[2] <= 32 && (size_t)ny * nx < ((size_t)1 << 31) && !MI_PROBE_ENV("MI_SEP_RING");
+    r.kzb = !r.acc ? 0 : k[2] <= 8 ? 8 : k[2] <= 16 ? 16 : 32;
+    r.lds = r.acc ? sep_lds_bytes_acc(k, offs) : sep_lds_bytes(k, offs);
+    return r;
+}
+
 int sep3d_launch(hipStream_t s, const float* in, float* out, int nx, int ny, int nz, const SepTaps taps[3], const int* offs, const int* bnd3,
                  int epi_kind, const ConvEpilogue& epi) {
     const int k[3] = {taps[0].n, taps[1].n, taps[2].n};
@@ -390,25 +408,21 @@ int sep3d_launch(hipStream_t s, const float* in, float* out, int nx, int ny, int
                "separable convolution: unknown epilogue %d", epi_kind);
     MI_REQUIRE(epi_kind == EPI_NONE || epi.a, "separable convolution: the epilogue needs its operand");
     MI_REQUIRE(epi_kind != EPI_UPDATE_REG || epi.b, "separable convolution: the regularised update needs its second operand");
-    SepGeom g{nx, ny, nz, offs[0], offs[1], offs[2], bnd3[0], bnd3[1], bnd3[2], 0};
-    // chunks along z: long enough that the kz - 1 planes of run-in are a small share, short enough to fill the device
-    const int tiles_xy = ((nx + SF_TX - 1) / SF_TX) * ((ny + SF_TY - 1) / SF_TY);
-    int zchunk = std::max(64, 8 * k[2]);
-    while (zchunk > 2 * k[2] && zchunk > 16 && (size_t)tiles_xy * ((nz + zchunk - 1) / zchunk) < 1024) zchunk /= 2;
-    g.zchunk = std::min(zchunk, nz);
-    const int total = tiles_xy * ((nz + g.zchunk - 1) / g.zchunk);
-    const bool wide = sep_patch_quads(k, offs) > 3 * SF_THREADS;
+    const SepRoute r = sep3d_route(nx, ny, nz, k, offs);
+    SepGeom g{nx, ny, nz, offs[0], offs[1], offs[2], bnd3[0], bnd3[1], bnd3[2], r.zchunk};
+    const int total = r.tiles_xy * r.chunks;
+    const bool wide = r.npre == 6;
     const dim3 grid((unsigned)((total + 7) / 8 * 8));
-    if (k[2] <= 32 && (size_t)ny * nx < ((size_t)1 << 31) && !MI_PROBE_ENV("MI_SEP_RING")) {  // z window in registers (k_sep3d_acc); MI_SEP_RING=1 (probes build): the LDS-ring kernel
-        const size_t lds_a = sep_lds_bytes_acc(k, offs);
+    if (r.acc) {  // z window in registers (k_sep3d_acc)
+        const size_t lds_a = r.lds;
         SepTaps tzr{};
         tzr.n = k[2];
         for (int j = 0; j < k[2]; ++j) tzr.w[j] = taps[2].w[k[2] - 1 - j];
 #define MI_SEPA3(E, NP, KB) hipLaunchKernelGGL((k_sep3d_acc<E, NP, KB>), grid, dim3(SF_THREADS), lds_a, s, in, out, epi, g, taps[0], taps[1], tzr)
 #define MI_SEPA2(E, NP)                                                                     \
     do {                                                                                    \
-        if (k[2] <= 8) MI_SEPA3(E, NP, 8);                                                  \
-        else if (k[2] <= 16) MI_SEPA3(E, NP, 16);                                           \
+        if (r.kzb == 8) MI_SEPA3(E, NP, 8);                                                 \
+        else if (r.kzb == 16) MI_SEPA3(E, NP, 16);                                          \
         else MI_SEPA3(E, NP, 32);                                                           \
     } while (0)
 #define MI_SEPA(E)                                                                          \
@@ -425,7 +439,7 @@ int sep3d_launch(hipStream_t s, const float* in, float* out, int nx, int ny, int
 #undef MI_SEPA3
         return launch_check("k_sep3d_acc");
     }
-    const size_t lds = sep_lds_bytes(k, offs);
+    const size_t lds = r.lds;
     MI_REQUIRE(lds <= kSepLdsMax, "separable convolution: the plane ring of %d taps does not fit the LDS (planes of 2^31 samples and more take the ring kernel)", k[2]);
 #define MI_SEP(E)                                                                                                                  \
     case E:                                                                                                                        \

@@ -360,6 +360,21 @@ class RLContext:
         """... and does so in one pass over the volume (``mi_rl_separable`` == 2)."""
         return int(lib().mi_rl_separable(self._h)) == 2
 
+    SEP_ROUTE_FIELDS = ("family", "kzb", "npre", "zchunk", "chunks", "lds_bytes")
+
+    def sep_route(self, adjoint=False):
+        """The build of the single-pass separable kernel that ``forward_ratio`` (``adjoint=True``: ``adjoint_update``) launches
+        (``mi_rl_sep_route``): ``family`` "acc" (z window in registers, ``kzb`` 8, 16 or 32) or "ring" (LDS ring of planes,
+        ``kzb`` 0), ``npre``, the planes of a z chunk, the chunk count and the dynamic LDS bytes; ``None`` when the context does
+        not take the single-pass route."""
+        out = (C.c_int * 6)()
+        check(lib().mi_rl_sep_route(self._h, int(bool(adjoint)), out))
+        if out[0] == 0:
+            return None
+        r = dict(zip(self.SEP_ROUTE_FIELDS, (int(v) for v in out)))
+        r["family"] = "acc" if out[0] == 1 else "ring"
+        return r
+
     @property
     def pair_layout(self) -> bool:
         """The FFT engine keeps the spectra around its z pass pair-interleaved (``mi_rl_pair_layout``)."""

@@ -130,6 +130,12 @@ int mi_rl_create_ex(int dev, void* stream, int nx, int ny, int nz, const float* 
  * 8 B/voxel; rows of whole float4, <= 51 taps per axis, a ring of kz xy-filtered planes in LDS); 1: three launches of the
  * dense kernel with 1-D tap tables (24 B/voxel; MI_NO_SEP_SINGLE=1 forces it).  MI_NO_SEPARABLE=1 disables the test. */
 int mi_rl_separable(const mi_rl_ctx* ctx);
+/* Which build of the single-pass kernel the forward (adjoint == 0) or adjoint convolution of the context launches on 16-byte
+ * aligned arrays, from the function the launch itself is decided by (host arithmetic).  out = six ints: family (0: the context
+ * does not take the single-pass route, mi_rl_separable != 2, and the rest is 0; 1: k_sep3d_acc, the z window in registers;
+ * 2: k_sep3d, the LDS ring of planes), KZB (register window 8, 16 or 32; 0 for the ring kernel), NPRE (float4 of the staged patch
+ * per thread: 3 or 6), planes per z chunk, number of z chunks, dynamic LDS bytes. */
+int mi_rl_sep_route(const mi_rl_ctx* ctx, int adjoint, int* out);
 /* 1 when the FFT engine of the context keeps its spectra around the z pass in the pair-interleaved layout (every block of 8 lines
  * followed by its 8 mirror-partner lines; two 64-KB z tiles per CU): z extents 2^a (64..1024), 3 * 2^a (192..768) or 9 * 2^a (576, 1152) on the hand-written
  * pipeline.  MI_FFT_NO_PAIR=1 keeps the plain layout [no reference counterpart: cuFFT owns its layouts]. */

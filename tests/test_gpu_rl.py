@@ -492,8 +492,9 @@ def test_separable_single_pass_variants(dev, boundary, kshape, monkeypatch):
 @pytest.mark.parametrize("boundary", [0, 1, 2])
 def test_separable_single_pass_edges_and_regularised_update(dev, boundary):
     """The single-pass separable kernel where its tiles are ragged: extents that are no multiples of the 64 x 16 tile, fewer planes
-    than taps along z, a z chunk boundary inside the volume, the regularised update epilogue (lambda > 0) -- against the dense
-    loop of the same engine and the oracle's whole deconSpatial / deconFFT run."""
+    than taps along z (9 or 12 planes under 11 taps: ONE z chunk -- the chunk seams are covered by tests/test_gpu_sep3d_operator.py),
+    the regularised update epilogue (lambda > 0) -- against the dense loop of the same engine and the oracle's whole deconSpatial /
+    deconFFT run."""
     from ipp_amd import decon
     shape, kshape = ((9, 23, 68), (11, 5, 7)) if boundary != 2 else ((12, 23, 68), (11, 5, 7))   # (circular: the PSF fits the shape)
     psf = R.gaussian_psf(kshape, (2.0, 1.0, 1.5))
