@@ -13,6 +13,7 @@
 // renumbered so that groups resident on one XCD walk z first: the kz input planes of a column are
 // then shared through that XCD's L2 instead of being re-fetched.
 #include "conv3d_direct.h"
+#include "fftconv.h"  // the FFT branch of mi_conv3d
 
 namespace mi {
 namespace {
@@ -271,3 +272,48 @@ int direct_conv_launch(hipStream_t s, const float* img, const float* kf, float* 
 }
 
 }  // namespace mi
+
+// ------------------------------------------------------------------------------------------------
+// The one-shot convolution entry: either engine, prepared, run and waited for in one call
+using namespace mi;
+
+extern "C" int mi_conv3d(int dev, void* stream, const float* img, const float* ker, float* out, int nx, int ny, int nz, int kx, int ky,
+                         int kz, int boundary, int engine) {
+    MI_TRY(use_device(dev));
+    MI_REQUIRE(img && ker && out && img != out, "conv3d: null or aliased pointers");
+    MI_REQUIRE(nx > 0 && ny > 0 && nz > 0, "conv3d_gpu:Input: Image must be 3D gpuArray single.");
+    MI_REQUIRE(kx > 0 && ky > 0 && kz > 0, "conv3d_gpu:Kernel: Kernel must be 3D gpuArray single.");
+    MI_REQUIRE(boundary >= MI_BOUNDARY_ZERO && boundary <= MI_BOUNDARY_CIRCULAR, "conv3d: unknown boundary rule %d", boundary);
+    hipStream_t s = as_stream(stream);
+    if (engine == MI_ENGINE_AUTO) engine = mi_engine_select(nx, ny, nz, kx, ky, kz, boundary);
+    ConvEpilogue e;
+    int rc;
+    if (engine == MI_ENGINE_DIRECT) {
+        DevBuf kf;
+        int kxp = 0;
+        rc = direct_prepare_psf(s, ker, kx, ky, kz, false, true, kf, &kxp);
+        if (rc == MI_OK) rc = direct_conv_launch(s, img, kf.as<float>(), out, nx, ny, nz, kx, ky, kz, kxp, boundary, EPI_NONE, e);
+        hipError_t he = hipStreamSynchronize(s);  // kf dies at scope exit
+        if (rc == MI_OK && he != hipSuccess) rc = fail(MI_ERR_HIP, "conv3d: %s", hipGetErrorString(he));
+        return rc;
+    }
+    MI_REQUIRE(engine == MI_ENGINE_FFT, "conv3d: engine %d not available", engine);
+    FftEngine fe;
+    const int n[3] = {nx, ny, nz}, k[3] = {kx, ky, kz}, b[3] = {boundary, boundary, boundary};
+    int shift[3];
+    for (int d = 0; d < 3; ++d) {
+        MI_REQUIRE(boundary != MI_BOUNDARY_CIRCULAR || k[d] <= n[d], "conv3d: kernel larger than the circular shape on axis %d", d);
+        // a plain circular convolution is centred like convn (no deconFFT placement quirk)
+        shift[d] = k[d] - 1 - conv_kernel_offset(k[d], boundary);
+    }
+    rc = fe.init(s, n, k, b, shift, ker, nullptr, /*need_adjoint=*/false);
+    if (rc == MI_OK) rc = fe.conv(s, img, false, out, EPI_NONE, e);
+    hipError_t he = hipStreamSynchronize(s);
+    if (rc == MI_OK && he != hipSuccess) rc = fail(MI_ERR_HIP, "conv3d: %s", hipGetErrorString(he));
+    return rc;
+}
+
+extern "C" int mi_conv3d_replicate(int dev, void* stream, const float* img, const float* ker, float* out, int nx, int ny, int nz, int kx,
+                                   int ky, int kz) {
+    return mi_conv3d(dev, stream, img, ker, out, nx, ny, nz, kx, ky, kz, MI_BOUNDARY_REPLICATE, MI_ENGINE_DIRECT);
+}

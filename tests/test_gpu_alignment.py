@@ -166,7 +166,7 @@ def test_norm2_refuses_an_offset_volume(dev, g, off):
 
 
 def test_stop_criterion_norm_on_an_offset_volume(dev, g):
-    """The stop test of the deconvolution loops takes the norm of the caller's volume as it is (rl.hip, host_norm): k_sumsq goes
+    """The stop test of the deconvolution loops takes the norm of the caller's volume as it is (rl_decon.hip, host_norm): k_sumsq goes
     element by element over a base that is not 16-byte aligned.  Same run as test_decon_stop_criterion_and_numpy_roundtrip."""
     from ipp_amd import decon
     psf = R.gaussian_psf((5, 5, 5), (1, 1, 1))

@@ -2,6 +2,8 @@
 Tolerance for floating point (BASELINE.json north_star: 1e-4 relative): tests/rl_util.py:assert_close -- 1e-4 of the
 maximum AND relative L2 < 1e-5 AND point-wise |d| <= 1e-4 |want| + 1e-7; tighter where the reference's own scripts
 use a tighter bound.  The unstable Wiener variant keeps the max-relative metric (see below)."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -162,8 +164,10 @@ def test_decon_spatial_matches_oracle(dev, engine, niter, lam, interval):
 
 
 @pytest.mark.parametrize("F_xyz", [None, (48, 40, 24)])
-@pytest.mark.parametrize("niter,lam,interval", [(5, 0.0, 0), (7, 0.05, 2)])
+@pytest.mark.parametrize("niter,lam,interval", [(5, 0.0, 0), (7, 0.0, 3), (7, 0.05, 2)])
 def test_decon_fft_matches_oracle(dev, F_xyz, niter, lam, interval):
+    # (7, 0.0, 3): a schedule without the Tikhonov term -- on the fused pipeline the regularisation Gaussian leaves the estimate in
+    # the scratch volume, the loop copies it home and (padded grid) the crop reads it there
     from ipp_amd import decon
     vol, psf = _case((20, 36, 44), (7, 5, 5), (1.5, 1.0, 1.0), 12)
     Fz = vol.shape if F_xyz is None else (F_xyz[2], F_xyz[1], F_xyz[0])
@@ -331,6 +335,54 @@ def test_decon_stop_criterion_and_numpy_roundtrip(dev):
     got, it = decon.decon(vol, psf, 50, 0.0, 5.0, 0, 1, False, None, False, return_iters=True)
     assert isinstance(got, np.ndarray) and it == it_want
     assert_close(got, want)
+
+
+# deconFFT's stop test (decon.m:189-196). The criteria come from the float64 oracle alone: for _case((12, 16, 16), (5, 5, 5),
+# (2, 2, 2), 6) and niter = 50 its relative change of ||bl||_2 per iteration, in percent, from iteration 1 on is
+#   F = the volume,   interval 0:  2.574 3.626 4.084 3.327 1.974 1.678 ..                               k =  5: 3.3269 -> 1.9744, c = 2.563
+#   F = (32, 32, 16), interval 0: 13.74 26.27 33.32 37.01 39.37 38.91 35.12 30.23 26.16 23.41 21.60 ..  k = 10: 26.159 -> 23.415, c = 24.749
+#   F = (32, 32, 16), interval 2: 13.74 16.52 31.01 19.61 37.40 18.16 37.15 10.82 28.42 2.800 21.63 ..  k = 10: 28.425 -> 2.8000, c = 8.921
+# c is the geometric mean of the changes at k - 1 and k, which differ by more than 10 %; the changes of iterations 2 .. k - 1 all lie
+# above c (the first is exempt: decon.m:194), so the oracle stops at k, and no change is closer than 5 % to c: float32 rounding of
+# the device's norms cannot move the count.  With interval 2 every iteration is its own mi_rl_iterate call.
+_STOP_F = (32, 32, 16)
+_STOP_CASES = {"unpadded": (None, 0, 2.563, 5), "padded": (_STOP_F, 0, 24.749, 10), "padded_interval_2": (_STOP_F, 2, 8.921, 10)}
+
+
+@functools.lru_cache(maxsize=None)
+def _stop_case(name):
+    F_xyz, interval, c, k = _STOP_CASES[name]
+    vol, psf = _case((12, 16, 16), (5, 5, 5), (2, 2, 2), 6)
+    want, it_want = R.decon_fft(vol, psf, vol.shape if F_xyz is None else F_xyz[::-1], 50, 0.0, c, interval, return_iters=True)
+    assert it_want == k
+    want.setflags(write=False)
+    return vol, psf, want
+
+
+@pytest.mark.parametrize("name", list(_STOP_CASES))
+def test_decon_fft_stop_criterion(dev, name):
+    from ipp_amd import decon
+    F_xyz, interval, c, k = _STOP_CASES[name]
+    vol, psf, want = _stop_case(name)
+    got, it = decon.decon(_t(vol, dev), psf, 50, 0.0, c, interval, 1, True, F_xyz or vol.shape[::-1], False, return_iters=True)
+    got = got.cpu().numpy()
+    print(name, "iterations", it, "of", k, "max rel", _rel(got, want))
+    assert it == k
+    assert_close(got, want)
+
+
+def test_decon_plan_with_a_stop_criterion(dev):
+    """The stop test through a plan: the same count and bits as the plain call, for a repeated padded deconFFT block and for a
+    deconSpatial call that makes the plan rebuild."""
+    from ipp_amd import decon
+    F_xyz, _, c, k = _STOP_CASES["padded"]
+    vol, psf, _ = _stop_case("padded")
+    with decon.DeconPlan(1) as plan:
+        for use_fft, fshape, crit in ((True, F_xyz, c), (True, F_xyz, c), (False, None, _STOP_CASES["unpadded"][2])):
+            want, it_want = decon.decon(_t(vol, dev), psf, 50, 0.0, crit, 0, 1, use_fft, fshape, False, return_iters=True)
+            got, it = decon.decon(_t(vol, dev), psf, 50, 0.0, crit, 0, 1, use_fft, fshape, False, return_iters=True, plan=plan)
+            assert it == it_want and (not use_fft or it == k)
+            assert np.array_equal(got.cpu().numpy(), want.cpu().numpy())
 
 
 def test_decon_config1_shape_parity(dev):
