@@ -50,8 +50,8 @@ Steps 5 and 6 are drop-ins for ``terastitcher -5 / -6`` (project files only):
                                 [--slicewidth W --sliceheight H --D0 z0 --D1 z1 --algorithm SINBLEND|NOBLEND] [--resolutions 0]
 
 Step 5 is the MST placement (TPAlgoMST::execute, host); step 6 merges the placed stacks on the device (include/mi_stitch.h) and
-writes the reference's RES(VxHxD)/V/V_H/V_H_D.tif tree at resolution 0.  The interactive pipeline around the steps stays with
-the reference's tools.
+writes the reference's RES(VxHxD)/V/V_H/V_H_D.tif tree at resolution 0.  The pipeline around the steps -- the reference's
+``process_images.py --input ACQ --tmptif TMP --stitched OUT --objective 15x`` -- is ``ipp_amd.acquisition`` (acquisition.py).
 With ``torchrun`` the pairs of a layer are dealt round-robin to the ranks (no collective; the per-rank XML fragments
 are merged by rank 0, like Parastitcher's mergedisplacements); under step 6 each rank writes a contiguous range of output slices.
 """
