@@ -182,6 +182,7 @@ SIGNATURES = {
     "mi_cached_memory_bytes": (_sz, []),
     "mi_rl_fuses": (_i, [_vp]),
     "mi_rl_otf_is_real": (_i, [_vp]),
+    "mi_rl_otf_form": (_i, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mi_rl_fft_route": (_i, [_vp, C.POINTER(FftRoute)]),
     "mi_rl_sharded_begin": (_i, [_vp, _vp, _vp]),
     "mi_rl_sharded_ratio": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_int)]),

@@ -37,6 +37,11 @@ struct NativeFft {
     float2* t_spec = nullptr;  // the second spectrum array T (inside S's allocation, or place.T2 when the arrays were placed by trial)
     DevBuf Gr, Gr_adj, ph;  // real form of the OTF(s) + phase tables (symmetric PSFs), see try_real_otf
     bool real_otf = false;
+    // the real OTF(s) as rank-R factors (otf_factor.h): per slot the four A_r by z position, then the four Bh_r of every line (xk, py,
+    // side); Gr / Gr_adj are released when these are adopted (try_factored_otf)
+    DevBuf Gf, Gf_adj;
+    int otf_rank = 0, otf_rank_adj = 0;  // 0: not factored
+    bool otf_factored() const { return otf_rank > 0; }
     bool have_adj = false;  // adjoint = second OTF (G_adj) instead of conj(G)
     const float2* tw_x = nullptr;
     const float2* tw_y = nullptr;
@@ -59,6 +64,9 @@ struct NativeFft {
     float4* otf() { return G.as<float4>(); }
     // after build_otf: switch to the real OTF form when the PSF allows it (delta: centre offset from the grid origin)
     int try_real_otf(hipStream_t s, const int delta[3]);
+    // after try_real_otf adopted the real form: factor the PSF(s) (device pointers, extents k = (x, y, z), centre offset delta as for try_real_otf) and, when the tables rebuild
+    // Gr to the criterion of the real form itself, keep the tables instead of the arrays.  `scale`: the scale build_otf was given.
+    int try_factored_otf(hipStream_t s, const float* psf, const float* psf_adj, const int k[3], const int delta[3], float scale);
     float* scratch() { return reinterpret_cast<float*>(t_spec); }  // F floats, free between convolutions
     // after the OTFs are built: volumes handed to conv / iterate have extents n (x, y, z) and are padded on the fly
     void set_window(const int n[3], const int o[3], const int rep[3], const int k[3]);
@@ -70,7 +78,7 @@ struct NativeFft {
     size_t spectrum_bytes() const { return spec_bytes; }   // one of the two spectrum arrays
     size_t spectrum_row_floats() const { return (size_t)2 * dims.nz * dims.hx; }
     size_t device_bytes() const {
-        return S.bytes + place.T2.bytes + place.S_alt.bytes + G.bytes + G_adj.bytes + Gr.bytes + Gr_adj.bytes + ph.bytes + tw.bytes;
+        return S.bytes + place.T2.bytes + place.S_alt.bytes + G.bytes + G_adj.bytes + Gr.bytes + Gr_adj.bytes + Gf.bytes + Gf_adj.bytes + ph.bytes + tw.bytes;
     }
 
     // ---- the passes (fft_native_x.hip, fft_native_yz.hip)

@@ -47,6 +47,7 @@ static NativeSwitches read_switches() {
     w.no_xpipe = set("MI_FFT_NO_XPIPE");
     w.no_prune = set("MI_FFT_NO_PRUNE");
     w.complex_otf = set("MI_FFT_COMPLEX_OTF");
+    w.stored_otf = set("MI_FFT_STORED_OTF");
     if (const char* e = std::getenv("MI_X_DYN")) w.x_dyn = atoi(e) != 0;
     if (const char* e = std::getenv("MI_Z_DYN")) w.z_dyn = atoi(e) != 0;
     w.place_min = mb("MI_FFT_PLACE_MIN_MB", w.place_min);

@@ -56,6 +56,7 @@ struct NativeSwitches {
     bool no_xpipe = false;     // MI_FFT_NO_XPIPE: whole x passes through the unpipelined kernels (every stage in LDS)
     bool no_prune = false;     // MI_FFT_NO_PRUNE: padded grids keep the full passes
     bool complex_otf = false;  // MI_FFT_COMPLEX_OTF: never the real form of the OTF
+    bool stored_otf = false;   // MI_FFT_STORED_OTF: the real form stays a stored array, never its rank-4 factors (A/B measurements)
     int x_dyn = -1, z_dyn = -1;  // MI_X_DYN / MI_Z_DYN: tiles of the persistent x / paired z launches from a device counter (1) or at a fixed stride (0); -1 unset
     size_t place_min = (size_t)6 << 30;  // MI_FFT_PLACE_MIN_MB: the smallest arrays (both together) placed by trial
     size_t alt_min = (size_t)8 << 30;    // MI_FFT_PLACE_ALT_MIN_MB: the smallest array that keeps a second buffer for S
@@ -228,6 +229,17 @@ constexpr bool z_pair_takes(int l2, int r3, int* nth = nullptr, bool* ph = nullp
     MI_ZQ_CASES(MI_TAKES)
 #undef MI_TAKES
     return false;
+}
+// The paired z pass of this length can rebuild the real OTF from its rank-4 factors (k_z_pair_pipe<.., FACT>): the table of the four
+// A_r, 16 bytes per z position, must fit LDS where the z ramp's 8-byte table lay without costing a work-group per CU.  576-point
+// lines have no room for either table beside their 72-KB tile (two work-groups per CU), and the 16 rows of 1152 points leave 10 KB
+// of the 156: both lengths keep the stored real form.
+constexpr bool z_pair_factored(int l2, int r3) {
+    bool ph = false;
+    if (!z_pair_takes(l2, r3, nullptr, &ph) || !ph) return false;
+    const int L = r3 << l2;
+    const size_t stored = lds_bytes(2 * kPairLines, L) + 8 * (size_t)L, fact = lds_bytes(2 * kPairLines, L) + 16 * (size_t)L;
+    return fact <= (size_t)kLdsOneWg && std::min<size_t>(2, kLdsOneWg / fact) == std::min<size_t>(2, kLdsOneWg / stored);  // (the launch's per_cu)
 }
 // n = r3 * 2^l2 as the axis takes it
 constexpr bool split_axis(int n, int axis, int* r3, int* l2) {

@@ -4,6 +4,7 @@
 // inlines the always-inline building blocks in the order the unit first emits them, so what it makes of a z kernel depends on the
 // y kernels named before it (profiles/NOTES.md, "FFT source split").
 #include "fft_native_dev.h"
+#include "otf_factor.h"
 
 namespace mi {
 namespace {
@@ -436,6 +437,9 @@ struct RealOtf {
     const float2* ph_x;  // by xk
     const float2* ph_y;  // by ky
     const float2* ph_z;  // by kz
+    // the factored form (otf_factor.h; k_z_pair_pipe<.., FACT>): {Ra, Rb} = (sum_r A_r[pz] Bh_r[side A], sum_r A_r[pz] Bh_r[side B])
+    const float4* fa;    // [pz] the four A_r of a z position
+    const float4* fb;    // [xk][py][side] the four Bh_r of a line: the 8 floats of a line pair are contiguous
 };
 
 template <int LZ2, int R3, bool REALG>
@@ -686,7 +690,11 @@ __global__ __launch_bounds__(kThreadsXZ, kWavesXZ) void k_z_conv_pipe(const floa
 //   NT = 1024 (768, 1152 points): a wave owns one line; the point-wise step sits between two barriers.  (1024-point lines run on
 //     NT = 512 with 246 registers: see the launch.)
 //   Lines of 3 * 2^a / 9 * 2^a points carry the radix-3 / 9 stage in front (behind, inverse) of the power-of-two chain.
-template <int LZ2, int R3, bool REALG, int NT, int TL, bool PHL = true, bool TOPON = true>
+// FACT (with REALG): the real OTF is rebuilt from its rank-4 factors instead of being read -- 8 B instead of 10 B per voxel.  The
+// A_r table (16 B per z position) takes the place of the z ramp's table in LDS, which leaves the two work-groups per CU of the 64-KB
+// tiles; the ramp of the lane's positions comes from the L1-hot global table into the registers the stored entries arrived in, and
+// the eight Bh_r of the wave's line pair are a uniform load.  Four FMAs per entry more in the point-wise step.
+template <int LZ2, int R3, bool REALG, int NT, int TL, bool PHL = true, bool TOPON = true, bool FACT = false>
 __global__ __launch_bounds__(NT, (NT == 512 && (R3 << LZ2) > 576) ? 2 : kWavesXZ) void k_z_pair_pipe(const float2* __restrict__ S, float2* __restrict__ T, const float4* __restrict__ G,
                                                               NativeDims d, const float2* __restrict__ tw, int conj_otf, int ntiles, RealOtf ro,
                                                               int* __restrict__ tile_ctr) {
@@ -726,7 +734,11 @@ __global__ __launch_bounds__(NT, (NT == 512 && (R3 << LZ2) > 576) ? 2 : kWavesXZ
     // REALG: the z ramp by POSITION, behind the twiddle tables (stride-1 look-ups in the point-wise step; PHL = false when that
     // table would cost the second work-group of the CU: the ramp then comes from global memory, by frequency)
     float2* phl = twl + TW::total;
-    if constexpr (REALG && PHL) {
+    float4* atab = reinterpret_cast<float4*>(twl + TW::total);
+    static_assert(!FACT || (REALG && PHL && TW::total % 2 == 0 && (2 * TL * row_pitch(R3 << LZ2)) % 2 == 0), "the A table is float4-aligned, in place of phl");
+    if constexpr (FACT) {
+        for (int p = threadIdx.x; p < L; p += NT) atab[p] = ro.fa[p];
+    } else if constexpr (REALG && PHL) {
         for (int p = threadIdx.x; p < L; p += NT) phl[p] = ro.ph_z[pos2freq(p, LZ2, R3)];
     }
     const bool dyn = tile_ctr != nullptr;
@@ -770,12 +782,21 @@ __global__ __launch_bounds__(NT, (NT == 512 && (R3 << LZ2) > 576) ? 2 : kWavesXZ
         float4 gv[REALG ? 1 : NPG];
         float2 gr[REALG ? NPG : 1];
         float2 ph_xy = make_float2(1.0f, 0.0f);
+        float4 b_a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b_b = b_a;
         auto load_G = [&]() {
             const int tid = launder(threadIdx.x);
             const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
             const int line = WP ? wv : wv % TL, p0 = WP ? 0 : (wv / TL) * (L / 2);
             if constexpr (REALG) {
                 ph_xy = cmul(ro.ph_x[plane], ro.ph_y[y_pos2freq(py0 + line, d)]);
+            }
+            if constexpr (FACT) {  // gr[k]: the z ramp of position lane + 64 k (+ p0); b_a, b_b: the line's factors (wave-uniform)
+                const float4* bp = ro.fb + ((size_t)plane * M + py0 + line) * 2;
+                b_a = bp[0];
+                b_b = bp[1];
+#pragma unroll
+                for (int k = 0; k < NPG; ++k) gr[k] = ro.ph_z[pos2freq(p0 + (tid & 63) + 64 * k, LZ2, R3)];
+                return;
             }
             const size_t gl = g0 + (size_t)line * L + p0 + (tid & 63);
 #pragma unroll
@@ -834,7 +855,16 @@ __global__ __launch_bounds__(NT, (NT == 512 && (R3 << LZ2) > 576) ? 2 : kWavesXZ
                 const float2 wO = cmul(wx, O);
                 const float2 Xa = cadd(E, wO), Xb = csub(E, wO);
                 float2 Ya, Yb;
-                if constexpr (REALG) {
+                if constexpr (FACT) {
+                    float2 Pq = cmul(ph_xy, gr[k]);
+                    if (conj_otf) Pq.y = -Pq.y;
+                    const float4 A4 = atab[lane + hb];
+                    const float ga = fmaf(A4.w, b_a.w, fmaf(A4.z, b_a.z, fmaf(A4.y, b_a.y, A4.x * b_a.x)));
+                    const float gb = fmaf(A4.w, b_b.w, fmaf(A4.z, b_b.z, fmaf(A4.y, b_b.y, A4.x * b_b.x)));
+                    const float2 XaP = cmul(Xa, Pq), XbP = cmul(Xb, Pq);
+                    Ya = make_float2(XaP.x * ga, XaP.y * ga);
+                    Yb = make_float2(XbP.x * gb, XbP.y * gb);
+                } else if constexpr (REALG) {
                     float2 Pq = cmul(ph_xy, PHL ? phl[lane + hb] : ro.ph_z[pos2freq(lane + hb, LZ2, R3)]);
                     if (conj_otf) Pq.y = -Pq.y;
                     const float2 XaP = cmul(Xa, Pq), XbP = cmul(Xb, Pq);
@@ -934,7 +964,59 @@ RealOtf real_otf_args(const NativeFft& f, bool adj_slot) {
     ro.ph_x = f.ph.as<float2>();
     ro.ph_y = ro.ph_x + (f.dims.hx / 2 + 1);
     ro.ph_z = ro.ph_y + f.dims.ny;
+    if (f.otf_factored()) {
+        ro.fa = adj_slot ? f.Gf_adj.as<float4>() : f.Gf.as<float4>();
+        ro.fb = ro.fa + f.dims.nz;
+    }
     return ro;
+}
+
+// ---------------------------------------------------------------------------------------------- the factored real OTF: tables
+// (otf_factor.h has the model and the host half.)  All sums in double.
+// A_r by z POSITION from A_r by frequency: the z pass looks its entries up by position
+__global__ __launch_bounds__(256) void k_fact_a_table(const double* __restrict__ a_freq, float4* __restrict__ fa, NativeDims d) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= d.nz) return;
+    const double* a = a_freq + 4 * (size_t)pos2freq(p, d.lz2, d.r3z);
+    fa[p] = make_float4((float)a[0], (float)a[1], (float)a[2], (float)a[3]);
+}
+// Bh_r of the line (xk, py, side): kx = xk (side A) or xk + Hx (side B) -- the two spectrum entries Xa, Xb the point-wise step untangles
+// -- and ky = the frequency at position py; side B carries the sign the stored form carries (try_factored_otf).  cs: [kx < 2 nx][r][y]{C, S}, the x half of the cosine sum (otf_factor_B_x) times the scale.
+__global__ __launch_bounds__(256) void k_fact_b_table(const double2* __restrict__ cs, float4* __restrict__ fb, NativeDims d, int ky_psf, size_t total) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int side = (int)(i & 1);
+    const size_t ln = i >> 1;
+    const int py = (int)(ln % d.ny), xk = (int)(ln / d.ny), nx = d.hx / 2 + 1;
+    const int ky = y_pos2freq(py, d);
+    const double2* c = cs + (size_t)(xk + side * nx) * 4 * ky_psf;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int y = 0; y < ky_psf; ++y) {
+        const long long t = (((long long)ky * (y - ky_psf / 2)) % d.ny + d.ny) % d.ny;
+        double sn, cn;
+        sincospi(2.0 * (double)t / (double)d.ny, &sn, &cn);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] += cn * c[r * ky_psf + y].x - sn * c[r * ky_psf + y].y;
+    }
+    fb[i] = make_float4((float)acc[0], (float)acc[1], (float)acc[2], (float)acc[3]);
+}
+// largest |Gr - sum_r A_r Bh_r| and largest |Gr| over the whole array (float bits, atomic max)
+__global__ __launch_bounds__(256) void k_fact_compare(const float2* __restrict__ Gr, const float4* __restrict__ fa, const float4* __restrict__ fb,
+                                                       NativeDims d, size_t total, unsigned* __restrict__ stats) {
+    const int L = d.nz;
+    float max_d = 0.0f, max_g = 0.0f;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int pz = (int)(i % L);
+        const size_t ln = i / L;
+        const float4 a = fa[pz], ba = fb[2 * ln], bb = fb[2 * ln + 1];
+        const float2 g = Gr[i];
+        const float ga = fmaf(a.w, ba.w, fmaf(a.z, ba.z, fmaf(a.y, ba.y, a.x * ba.x)));
+        const float gb = fmaf(a.w, bb.w, fmaf(a.z, bb.z, fmaf(a.y, bb.y, a.x * bb.x)));
+        max_d = fmaxf(max_d, fmaxf(fabsf(g.x - ga), fabsf(g.y - gb)));
+        max_g = fmaxf(max_g, fmaxf(fabsf(g.x), fabsf(g.y)));
+    }
+    atomicMax(&stats[0], __float_as_uint(max_d));
+    atomicMax(&stats[1], __float_as_uint(max_g));
 }
 
 // the paired z pass: one case per length of MI_ZQ_CASES (fft_native_route.h), with its threads per work-group and its PHL flag
@@ -997,7 +1079,8 @@ int NativeFft::z_conv(hipStream_t s, bool conj_otf, const float2* src_o, float2*
             const int ntiles = xkn * (M / kPairLines);
             bool phl = true;  // (576-point lines have no LDS phase table: MI_ZQ_CASES)
             z_pair_takes(dims.lz2, dims.r3z, nullptr, &phl);
-            const size_t lds = lds_bytes(2 * kPairLines, L) + (real_otf && phl ? sizeof(float2) * (size_t)L : 0);
+            const bool fact = real_otf && otf_factored();  // (the A_r table in place of the z ramp's: z_pair_factored)
+            const size_t lds = lds_bytes(2 * kPairLines, L) + (fact ? sizeof(float4) * (size_t)L : real_otf && phl ? sizeof(float2) * (size_t)L : 0);
             const int per_cu = std::max(1, std::min(2, (int)(kLdsOneWg / lds)));  // 8 waves of 128 registers each: two fit a CU
             const unsigned grid = (unsigned)std::min(ntiles, per_cu * n_cu);
             int* ctr_p = nullptr;
@@ -1009,6 +1092,11 @@ int NativeFft::z_conv(hipStream_t s, bool conj_otf, const float2* src_o, float2*
             return z_pair_case(dims, [&](auto lg, auto r, auto nth, auto ph_lds) {
                 constexpr int LG = lg(), R = r(), NTH = nth();
                 constexpr bool PH = ph_lds();
+                if constexpr (z_pair_factored(LG, R)) {
+                    if (fact)
+                        return launch_lds(k_z_pair_pipe<LG, R, true, NTH, kPairLines, PH, true, true>, grid, NTH, lds, s, "k_z_pair_pipe<factored OTF>",
+                                          Tp, Sp, Gp, d, twz, cj, ntiles, ro, ctr_p);
+                }
                 return real_otf ? launch_lds(k_z_pair_pipe<LG, R, true, NTH, kPairLines, PH>, grid, NTH, lds, s, "k_z_pair_pipe<real OTF>", Tp, Sp, Gp,
                                              d, twz, cj, ntiles, ro, ctr_p)
                                 : launch_lds(k_z_pair_pipe<LG, R, false, NTH, kPairLines, PH>, grid, NTH, lds, s, "k_z_pair_pipe", Tp, Sp, Gp, d,
@@ -1084,6 +1172,77 @@ int NativeFft::try_real_otf(hipStream_t s, const int delta[3]) {
         Gr.release();
         Gr_adj.release();
         ph.release();
+    }
+    return MI_OK;
+}
+
+// Tries the factored form of the real OTF(s) (otf_factor.h) where the z route is the paired pipelined kernel of a length that takes it
+// (z_pair_factored; the plain-layout kernels keep the stored form).  Per slot: factor the PSF on the host, build the tables, and compare
+// sum_r A_r Bh_r with the Gr that try_real_otf stored, entry by entry -- adopted when they differ by at most 4e-6 of the largest entry, the
+// criterion of the real form itself (the difference is the float32 rounding of the transform that built Gr).  Adopted: Gr is released;
+// otherwise the tables are, and the plan goes on with the stored form.
+int NativeFft::try_factored_otf(hipStream_t s, const float* psf, const float* psf_adj, const int k[3], const int delta[3], float scale) {
+    if (!real_otf || sw.stored_otf || z_route(dims, sw, true) != ZRoute::pair_pipe_real || !z_pair_factored(dims.lz2, dims.r3z)) return MI_OK;
+    MI_REQUIRE(have_adj == (psf_adj != nullptr), "native FFT: the factored OTF needs the PSF of every slot");
+    const int Hx = dims.hx, M = dims.ny, L = dims.nz, nx = Hx / 2 + 1, slots = have_adj ? 2 : 1;
+    const size_t nk = (size_t)k[0] * k[1] * k[2], lines = (size_t)nx * M, total = lines * L;
+    std::vector<float> hpsf(nk);
+    int ranks[2] = {0, 0};
+    DevBuf st, da, dcs;
+    MI_TRY(st.alloc(4 * sizeof(unsigned)));
+    MI_HIP(hipMemsetAsync(st.p, 0, 4 * sizeof(unsigned), s));
+    MI_TRY(da.alloc(sizeof(double) * 4 * (size_t)L));
+    MI_TRY(dcs.alloc(sizeof(double) * 2 * (size_t)(2 * nx) * 4 * k[1]));
+    std::vector<double> ha(4 * (size_t)L), hcs(2 * (size_t)(2 * nx) * 4 * k[1]), C(k[1]), S(k[1]);
+    bool ok = true;
+    for (int slot = 0; slot < slots && ok; ++slot) {
+        MI_HIP(hipMemcpyAsync(hpsf.data(), slot ? psf_adj : psf, sizeof(float) * nk, hipMemcpyDeviceToHost, s));
+        MI_HIP(hipStreamSynchronize(s));
+        const OtfFactors f = otf_factor(hpsf.data(), k[0], k[1], k[2]);
+        ranks[slot] = f.rank;
+        if (f.rank == 0) { ok = false; break; }
+        for (int kz = 0; kz < L; ++kz)
+            for (int r = 0; r < kOtfMaxRank; ++r) ha[4 * (size_t)kz + r] = r < f.rank ? otf_factor_A(f, r, kz, L) : 0.0;
+        for (int side = 0; side < 2; ++side)
+            for (int xk = 0; xk < nx; ++xk)
+                for (int r = 0; r < kOtfMaxRank; ++r) {
+                    otf_factor_B_x(f, r, xk + side * Hx, 2 * Hx, C.data(), S.data());
+                    double* dst = &hcs[2 * (((size_t)(xk + side * nx) * 4 + r) * k[1])];
+                    // (side B: the stored form removes the ramp of xk, not of xk + Hx -- the two differ by exp(-pi i delta_x), a sign)
+                    const double sc = (double)scale * (side && (delta[0] & 1) ? -1.0 : 1.0);
+                    for (int y = 0; y < k[1]; ++y) { dst[2 * y] = C[y] * sc; dst[2 * y + 1] = S[y] * sc; }
+                }
+        DevBuf& tab = slot ? Gf_adj : Gf;
+        MI_TRY(tab.alloc(sizeof(float4) * ((size_t)L + 2 * lines)));
+        MI_HIP(hipMemcpyAsync(da.p, ha.data(), sizeof(double) * ha.size(), hipMemcpyHostToDevice, s));
+        MI_HIP(hipMemcpyAsync(dcs.p, hcs.data(), sizeof(double) * hcs.size(), hipMemcpyHostToDevice, s));
+        float4* fa = tab.as<float4>();
+        float4* fb = fa + L;
+        hipLaunchKernelGGL(k_fact_a_table, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, s, da.as<double>(), fa, dims);
+        MI_TRY(launch_check("k_fact_a_table"));
+        hipLaunchKernelGGL(k_fact_b_table, dim3((unsigned)((2 * lines + 255) / 256)), dim3(256), 0, s, dcs.as<double2>(), fb, dims, k[1], 2 * lines);
+        MI_TRY(launch_check("k_fact_b_table"));
+        const size_t blocks = std::min<size_t>((total + 255) / 256, 256 * 16);
+        hipLaunchKernelGGL(k_fact_compare, dim3((unsigned)blocks), dim3(256), 0, s, (slot ? Gr_adj : Gr).as<float2>(), (const float4*)fa, (const float4*)fb,
+                           dims, total, st.as<unsigned>() + 2 * slot);
+        MI_TRY(launch_check("k_fact_compare"));
+        MI_HIP(hipStreamSynchronize(s));  // (the host tables are reused by the next slot)
+    }
+    float hs[4] = {0, 0, 0, 0};
+    MI_HIP(hipMemcpyAsync(hs, st.p, sizeof(hs), hipMemcpyDeviceToHost, s));
+    MI_HIP(hipStreamSynchronize(s));
+    ok = ok && hs[0] <= 4e-6f * hs[1] && (!have_adj || hs[2] <= 4e-6f * hs[3]);
+    if (sw.place_log)
+        fprintf(stderr, "native FFT: factored OTF ranks %d / %d, max|Gr - sum A B| %.3e of %.3e (adjoint %.3e of %.3e): %s\n", ranks[0], ranks[1],
+                (double)hs[0], (double)hs[1], (double)hs[2], (double)hs[3], ok ? "adopted" : "stored form kept");
+    if (ok) {
+        otf_rank = ranks[0];
+        otf_rank_adj = ranks[1];
+        Gr.release();
+        Gr_adj.release();
+    } else {
+        Gf.release();
+        Gf_adj.release();
     }
     return MI_OK;
 }

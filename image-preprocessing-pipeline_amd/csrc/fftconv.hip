@@ -388,6 +388,10 @@ int FftEngine::init(hipStream_t s, const int n[3], const int k[3], const int bnd
             MI_SPAN_BEGIN(sp2, "FftEngine: native real-OTF test");
             MI_TRY(native->try_real_otf(s, delta));
             MI_SPAN_END(sp2);
+            if (native->real_otf) {  // ... and the real form itself is a sum of at most four products A_r(kz) Bh_r(kx, ky) for every PSF of that model
+                const int kk[3] = {ax[0].k, ax[1].k, ax[2].k};
+                MI_TRY(native->try_factored_otf(s, psf, have_adj ? psf_inv : nullptr, kk, delta, nscale));
+            }
         }
         if (padded) {  // the x passes pad and crop on the fly: no staging volume
             int nn[3], oo[3], rep[3], kk[3];

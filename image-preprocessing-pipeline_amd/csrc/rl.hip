@@ -330,6 +330,13 @@ extern "C" int mi_rl_otf_is_real(mi_rl_ctx* ctx) {
     return native_of(ctx) && native_of(ctx)->real_otf ? 1 : 0;
 }
 
+extern "C" int mi_rl_otf_form(mi_rl_ctx* ctx, int* rank, int* rank_adj) {
+    const NativeFft* f = native_of(ctx);
+    if (rank) *rank = f ? f->otf_rank : 0;
+    if (rank_adj) *rank_adj = f ? f->otf_rank_adj : 0;
+    return !f || !f->real_otf ? 0 : f->otf_factored() ? 2 : 1;
+}
+
 extern "C" int mi_rl_fft_route(mi_rl_ctx* ctx, mi_fft_route* out) {
     MI_REQUIRE(ctx && out, "mi_rl_fft_route: null pointer");
     *out = mi_fft_route{};

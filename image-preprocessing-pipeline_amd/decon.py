@@ -385,6 +385,14 @@ class RLContext:
         return bool(lib().mi_rl_otf_is_real(self._h))
 
     @property
+    def otf_form(self) -> dict:
+        """``form``: "complex", "stored" (real, an array) or "factored" (real, rebuilt by the z pass from rank-R factors); ``rank`` and
+        ``rank_adj``: R of the OTF and of an explicit adjoint's, 0 when not factored."""
+        rank, rank_adj = C.c_int(0), C.c_int(0)
+        form = lib().mi_rl_otf_form(self._h, C.byref(rank), C.byref(rank_adj))
+        return {"form": ("complex", "stored", "factored")[form], "rank": rank.value, "rank_adj": rank_adj.value}
+
+    @property
     def fft_route(self) -> dict:
         """What the context's FFT plan does (``mi_rl_fft_route``): kernel family of the z pass, layouts, tile hand-out, tile sizes --
         decided from the environment at the moment the context was created."""

@@ -173,6 +173,10 @@ int mi_rl_fuses(mi_rl_ctx* ctx);
 /* 1 when the context keeps its OTF in the real form (PSF mirror-symmetric about its centre sample: 2 floats per spectrum pair
  * plus per-axis phase tables instead of 4 floats; the z pass then moves 10 instead of 12 bytes per voxel). */
 int mi_rl_otf_is_real(mi_rl_ctx* ctx);
+/* The form of the context's OTF: 0 complex, 1 real and stored, 2 real and rebuilt by the z pass from rank-R factors A_r(kz) Bh_r(kx, ky)
+ * (8 bytes per voxel in the z pass, no OTF array; MI_FFT_STORED_OTF=1 keeps form 1).  rank / rank_adj (may be NULL): R of the OTF and of
+ * the explicit adjoint's, 0 when not factored. */
+int mi_rl_otf_form(mi_rl_ctx* ctx, int* rank, int* rank_adj);
 /* What the context's FFT plan does, from the plan's own record (the switches are those of the environment at the moment the
  * context was created and hold for its whole life): native 1 = the hand-written pipeline (everything else is 0 when it is not);
  * paired = mi_rl_pair_layout; z_kernel 0 k_z_conv, 1 k_z_conv_pipe, 2 k_z_pair_pipe; real_otf = mi_rl_otf_is_real; x_pipelined 1 = a
