@@ -6,7 +6,13 @@
  *   local_percentile      :245-312   (one percentile, numpy.percentile's 'linear' method)
  *   apply_local_function  :113-237   (centres :168-175, clipped and stepped windows :193-198, scipy.ndimage.zoom(order=1) :218-229)
  * Not built (refused by the Python layer by name): masks, array-shaped windows, lists of percentiles, interpolation orders other
- * than 1 / None.  NaN samples are not ordered the way numpy orders them.
+ * than 1 / None.
+ *
+ * float32 samples must be FINITE.  Samples are ranked by their bit patterns (sign bit flipped, negative values wholly inverted):
+ * -0.0 sorts just below +0.0 (one value to numpy, so the percentile is the same) and denormals keep their place, but a NaN is
+ * ranked like a number -- above +inf, or below -inf when its sign bit is set -- and does not poison its window as it does in numpy
+ * (windows that do not hold it are the same in both).  At percentile 1 numpy forms inf - inf in its lerp and returns NaN for a
+ * window whose maximum is infinite; this library returns the maximum.
  *
  * Semantics kept: per axis `n = extent / spacing` centres at `left + i * spacing`, `left = (extent - (n - 1) *
  * spacing) / 2`; window [max(0, c - selem / 2), min(c + selem - selem / 2, extent)) walked with `step` from its clipped start; the
