@@ -115,7 +115,7 @@ ISO_MAX_STEPS = 32  # MI_ISO_MAX_STEPS
 class FftRoute(C.Structure):
     """mi_fft_route (include/mi_lsdeconv.h)"""
     _fields_ = [(name, C.c_int) for name in ("native", "paired", "z_kernel", "real_otf", "x_pipelined", "x_splits", "x_dynamic", "z_dynamic",
-                                              "pruned", "ty", "tc", "tl")]
+                                              "pruned", "ty", "tc", "tl", "z_full_grid")]
 
 
 class IsodownParams(C.Structure):

@@ -46,6 +46,7 @@ struct NativeFft {
     const float2* tw_x = nullptr;
     const float2* tw_y = nullptr;
     const float2* tw_z = nullptr;
+    const float2* tw_plane = nullptr;  // exp(-2 pi i xk / (2 Hx)), xk <= Hx/2, behind the axis tables in `tw` (fill_plane_twiddles: the paired z pass)
     size_t n_cplx = 0;
     size_t spec_bytes = 0;
     int n_cu = 256;  // persistent kernels launch one work-group per CU
@@ -82,6 +83,7 @@ struct NativeFft {
     }
 
     // ---- the passes (fft_native_x.hip, fft_native_yz.hip)
+    int fill_plane_twiddles(hipStream_t s, float2* dst);
     int x_forward(hipStream_t s, const float* in);
     int middle(hipStream_t s, bool conj_otf);
     int y_pass(hipStream_t s, bool inverse, YRoute route, const float2* src = nullptr, float2* dst = nullptr, int xk0 = 0, int xkn = -1);

@@ -48,6 +48,7 @@ static NativeSwitches read_switches() {
     w.no_prune = set("MI_FFT_NO_PRUNE");
     w.complex_otf = set("MI_FFT_COMPLEX_OTF");
     w.stored_otf = set("MI_FFT_STORED_OTF");
+    w.z_general = set("MI_FFT_Z_GENERAL");
     if (const char* e = std::getenv("MI_X_DYN")) w.x_dyn = atoi(e) != 0;
     if (const char* e = std::getenv("MI_Z_DYN")) w.z_dyn = atoi(e) != 0;
     w.place_min = mb("MI_FFT_PLACE_MIN_MB", w.place_min);
@@ -97,8 +98,9 @@ int NativeFft::init(hipStream_t s, const int F[3], bool explicit_adjoint) {
             for (int e = 0; e < lens[a]; ++e)
                 h[offs[a] + subs[a] / 2 + e] = make_float2((float)std::cos(two_pi * e / lens[a]), (float)-std::sin(two_pi * e / lens[a]));
     }
-    MI_TRY(tw.alloc(sizeof(float2) * off));
+    MI_TRY(tw.alloc(sizeof(float2) * (off + (size_t)(Hx / 2 + 1))));  // (behind the axis tables: the plane twiddles of the paired z pass)
     MI_HIP(hipMemcpyAsync(tw.p, h.data(), sizeof(float2) * off, hipMemcpyHostToDevice, s));
+    MI_TRY(fill_plane_twiddles(s, tw.as<float2>() + off));
     tw_x = tw.as<float2>() + offs[0];
     tw_y = tw.as<float2>() + offs[1];
     tw_z = tw.as<float2>() + offs[2];

@@ -307,7 +307,10 @@ __host__ __device__ constexpr int group_elem(int g) { return ((g >> S_LO) << (S_
 // One super-stage, everything about the transform compile-time: R = 2^LR points per lane, radix-2 stages
 // S_LO+LR-1..S_LO (forward, DIF) or S_LO..S_LO+LR-1 (inverse, DIT) on the sequences of the tile.
 // twl: the super-stage's LDS table of lane twiddles and their powers (see butterflies).
-template <int LOGN, int LR, int S_LO, bool INVERSE, int NT, int R3>
+// LIT (the paired z pass on power-of-two lines, whose tile is a static array): rows are a power of two long (pitch = row length), so
+// a row's base and a slot occupy disjoint bits and the BYTE address of register j is the lane's XOR one literal -- one instruction per
+// access where slot-then-scale takes two.
+template <int LOGN, int LR, int S_LO, bool INVERSE, int NT, int R3, bool LIT = false>
 __device__ __forceinline__ void super_stage(float2* tile, int batch, int pitch, int hp, bool priv, const float2* twl) {
     constexpr int R = 1 << LR, H_LO = 1 << S_LO, GL = LOGN - LR, NW = NT / 64;
     if constexpr (GL >= 6) {
@@ -333,6 +336,18 @@ __device__ __forceinline__ void super_stage(float2* tile, int batch, int pitch, 
             for (int gk = 0; gk < G; gk += coop) {
                 const int a0 = a_lane ^ (s_seq ^ swz_c(group_elem<LR, S_LO>(gk)));
                 float2 v[R];
+                if constexpr (LIT) {
+                    const unsigned ab = ((unsigned)(rowi * pitch) | (unsigned)a0) << 3;
+                    const auto reg = [&](int j) -> float2& {
+                        return *reinterpret_cast<float2*>(reinterpret_cast<char*>(tile) + (H_LO >= 256 ? ab + (unsigned)(j * H_LO) * 8u : ab ^ ((unsigned)swz_c(j << S_LO) << 3)));
+                    };
+#pragma unroll
+                    for (int j = 0; j < R; ++j) v[j] = reg(j);
+                    butterflies<LR, S_LO, INVERSE>(v, twl, m_lane | (gk & (H_LO - 1)));
+#pragma unroll
+                    for (int j = 0; j < R; ++j) reg(j) = v[j];
+                    continue;
+                }
 #pragma unroll
                 for (int j = 0; j < R; ++j) v[j] = H_LO >= 256 ? row[a0 + j * H_LO] : row[a0 ^ swz_c(j << S_LO)];
                 butterflies<LR, S_LO, INVERSE>(v, twl, m_lane | (gk & (H_LO - 1)));
@@ -371,14 +386,14 @@ __device__ __forceinline__ void super_stage(float2* tile, int batch, int pitch, 
 // full transform of the tile's sequences as the chain of super-stages; twl: the axis' LDS tables.  The caller synchronises
 // before (tile and tables filled): with a work-group barrier, or -- PRIV, and the rows were filled by their owners -- not at
 // all.  On return the tile is consistent for the work-group (!PRIV) or for each row's owner (PRIV).
-template <int LOGN, bool INVERSE, int NT, int R3 = 1, int DONE = 0, int STOP = LOGN, int CUT = 0>
+template <int LOGN, bool INVERSE, int NT, int R3 = 1, int DONE = 0, int STOP = LOGN, int CUT = 0, bool LIT = false>
 __device__ __forceinline__ void lds_fft(float2* tile, int batch, int pitch, int hp, bool priv, const float2* twl) {
     if constexpr (DONE < STOP) {
         constexpr int s_lo = INVERSE ? DONE : seg_below(LOGN, LOGN - DONE, CUT);  // forward: top stages first; inverse: bottom first
         constexpr int r = INVERSE ? seg_r(LOGN, DONE, CUT) : LOGN - DONE - s_lo;
-        super_stage<LOGN, r, s_lo, INVERSE, NT, R3>(tile, batch, pitch, hp, priv, twl + tw_off(LOGN, s_lo, CUT));
+        super_stage<LOGN, r, s_lo, INVERSE, NT, R3, LIT>(tile, batch, pitch, hp, priv, twl + tw_off(LOGN, s_lo, CUT));
         stage_sync(priv);
-        lds_fft<LOGN, INVERSE, NT, R3, DONE + r, STOP, CUT>(tile, batch, pitch, hp, priv, twl);
+        lds_fft<LOGN, INVERSE, NT, R3, DONE + r, STOP, CUT, LIT>(tile, batch, pitch, hp, priv, twl);
     }
 }
 

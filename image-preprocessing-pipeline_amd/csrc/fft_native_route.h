@@ -57,6 +57,7 @@ struct NativeSwitches {
     bool no_prune = false;     // MI_FFT_NO_PRUNE: padded grids keep the full passes
     bool complex_otf = false;  // MI_FFT_COMPLEX_OTF: never the real form of the OTF
     bool stored_otf = false;   // MI_FFT_STORED_OTF: the real form stays a stored array, never its rank-4 factors (A/B measurements)
+    bool z_general = false;    // MI_FFT_Z_GENERAL: the paired z pass keeps the plane bounds of a pruned grid on a full one (parity test, A/B measurements)
     int x_dyn = -1, z_dyn = -1;  // MI_X_DYN / MI_Z_DYN: tiles of the persistent x / paired z launches from a device counter (1) or at a fixed stride (0); -1 unset
     size_t place_min = (size_t)6 << 30;  // MI_FFT_PLACE_MIN_MB: the smallest arrays (both together) placed by trial
     size_t alt_min = (size_t)8 << 30;    // MI_FFT_PLACE_ALT_MIN_MB: the smallest array that keeps a second buffer for S
@@ -230,6 +231,15 @@ constexpr bool z_pair_takes(int l2, int r3, int* nth = nullptr, bool* ph = nullp
 #undef MI_TAKES
     return false;
 }
+// LDS of a work-group of the paired z pass, without its 4-byte tile counter: the tile of 2 * kPairLines rows and the twiddle tables, then
+// the table of the OTF form -- the four A_r (16 B per z position) of the factored form, or the z ramp (8 B) of the stored real form where
+// the length keeps one (PHL).  The kernel declares exactly this as a static array; the launch derives the work-groups per CU from it.
+constexpr size_t z_pair_lds(int l2, int r3, bool real_otf, bool factored) {
+    bool ph = false;
+    z_pair_takes(l2, r3, nullptr, &ph);
+    const int L = r3 << l2;
+    return lds_bytes(2 * kPairLines, L) + (factored ? 16 * (size_t)L : real_otf && ph ? 8 * (size_t)L : 0);
+}
 // The paired z pass of this length can rebuild the real OTF from its rank-4 factors (k_z_pair_pipe<.., FACT>): the table of the four
 // A_r, 16 bytes per z position, must fit LDS where the z ramp's 8-byte table lay without costing a work-group per CU.  576-point
 // lines have no room for either table beside their 72-KB tile (two work-groups per CU), and the 16 rows of 1152 points leave 10 KB
@@ -344,6 +354,12 @@ inline ZRoute z_route(const NativeDims& d, const NativeSwitches& sw, bool real_o
     return real_otf ? ZRoute::real_needs_pipe : ZRoute::conv;
 }
 inline YRoute y_route(const NativeDims& d) { return d.paired ? YRoute::pair : YRoute::pass; }
+// The paired z pass runs in its full-grid form, without plane bounds on its loads and stores: every z plane is read and written (a
+// circular grid, or a padded one whose window prunes nothing along z).  Any bound short of the grid, or MI_FFT_Z_GENERAL, keeps the
+// predicated form.
+inline bool z_full_grid(const NativeDims& d, const NativeSwitches& sw) {
+    return d.paired && !sw.z_general && d.z_in_hi == d.nz && d.z_out_lo == 0 && d.z_out_hi == d.nz;
+}
 
 inline bool pad_can_fuse(const PadWindow& pw) { return !pw.on || !(pw.rep[0] || pw.rep[1] || pw.rep[2]); }
 // padded grids take the persistent x kernels too: zero rule, data at the origin, whole float4 rows and what the call site asks

@@ -694,13 +694,26 @@ __global__ __launch_bounds__(kThreadsXZ, kWavesXZ) void k_z_conv_pipe(const floa
 // A_r table (16 B per z position) takes the place of the z ramp's table in LDS, which leaves the two work-groups per CU of the 64-KB
 // tiles; the ramp of the lane's positions comes from the L1-hot global table into the registers the stored entries arrived in, and
 // the eight Bh_r of the wave's line pair are a uniform load.  Four FMAs per entry more in the point-wise step.
-template <int LZ2, int R3, bool REALG, int NT, int TL, bool PHL = true, bool TOPON = true, bool FACT = false>
+// FULLZ: every z plane is read and written (a circular grid, or a padded one that prunes nothing): the fill and the drain carry no
+// plane bounds (z_full_grid, fft_native_route.h).  wxt: exp(-2 pi i xk / Nx) by plane (NativeFft::fill_plane_twiddles).
+template <int LZ2, int R3, bool REALG, int NT, int TL, bool PHL = true, bool TOPON = true, bool FACT = false, bool FULLZ = false>
 __global__ __launch_bounds__(NT, (NT == 512 && (R3 << LZ2) > 576) ? 2 : kWavesXZ) void k_z_pair_pipe(const float2* __restrict__ S, float2* __restrict__ T, const float4* __restrict__ G,
                                                               NativeDims d, const float2* __restrict__ tw, int conj_otf, int ntiles, RealOtf ro,
-                                                              int* __restrict__ tile_ctr) {
-    extern __shared__ __attribute__((aligned(16))) float2 tile[];
-    __shared__ int s_next_tile;  // tiles from a device counter when tile_ctr != nullptr (see k_x_fused_pipe)
+                                                              int* __restrict__ tile_ctr, const float2* __restrict__ wxt) {
     constexpr int L = R3 << LZ2, NW = NT / 64, hp = TL, pitch = row_pitch(L);
+    // All of the work-group's LDS as ONE static array -- tile, twiddle tables, the table of the OTF form, the tile counter -- so that the
+    // compiler knows every address as a number (behind a dynamic array's base each swizzled access costs a second instruction).  Its size
+    // is what the launch computes the work-groups per CU from (z_pair_lds); the launch passes no dynamic bytes.
+    constexpr size_t kLds = z_pair_lds(LZ2, R3, REALG, FACT);
+    static_assert(kLds == lds_bytes(2 * TL, L) + (FACT ? 16 : REALG && PHL ? 8 : 0) * (size_t)L && kLds % 16 == 0, "the static array is the launch's LDS figure");
+    __shared__ __attribute__((aligned(16))) unsigned char lds_all[kLds + sizeof(int)];
+    float2* const tile = reinterpret_cast<float2*>(lds_all);
+    int& s_next_tile = *reinterpret_cast<int*>(lds_all + kLds);  // tiles from a device counter when tile_ctr != nullptr (see k_x_fused_pipe)
+    // LIT: power-of-two lines (pitch = L): a row's base and a slot occupy disjoint bits, so every swizzled access is addressed by
+    // BYTE offset as (lane constant) XOR (literal), one instruction; lines of 3 * 2^a and 9 * 2^a points keep slot arithmetic
+    constexpr bool LIT = R3 == 1;
+    static_assert(!LIT || (pitch == L && (L & (L - 1)) == 0), "power-of-two lines are their own pitch");
+    const auto at = [&](unsigned byte_off) -> float2& { return *reinterpret_cast<float2*>(lds_all + byte_off); };
     // WP: every wave owns one A line and its partner (rows wave, TL + wave), so the point-wise step is wave-private too;
     // else (1024-point lines: 16 waves on 16 rows) a wave owns ONE row, the point-wise step of line `wave % TL` is shared by the
     // owners of its two rows -- half of the positions each -- and sits between two work-group barriers
@@ -712,7 +725,7 @@ __global__ __launch_bounds__(NT, (NT == 512 && (R3 << LZ2) > 576) ? 2 : kWavesXZ
     // the top super-stage of the chain (stages TOPS .. LZ2-1) works on elements z0 + k * 2^TOPS: exactly the items of a lane
     constexpr int TOPS = seg_below(LZ2, LZ2), TOPR = LZ2 - TOPS;
     constexpr bool TOPREG = TOPON && R3 == 1 && (1 << TOPS) == P && (1 << TOPR) == NPA;
-    const int Hx = d.hx, M = d.ny, ytiles = M / TL;
+    const int M = d.ny, ytiles = M / TL;
     const size_t ZR = (size_t)(M + d.zpad);  // float4 per row (xk, z) of the paired layout
     struct FView { int row, slot, z0; size_t off; };
     auto f_view = [&]() {
@@ -720,13 +733,25 @@ __global__ __launch_bounds__(NT, (NT == 512 && (R3 << LZ2) > 576) ? 2 : kWavesXZ
         const int z0 = tid / TL, jq = tid - z0 * TL;  // float4 jq of the segment: lines 2 jq, 2 jq + 1 (rows TL.. = B side)
         return FView{(2 * jq) * pitch, phys(z0) ^ rmask(2 * jq, hp), z0, (size_t)z0 * ZR + jq};
     };
+    // the cells of item k of the transposed view (lines 2 jq and 2 jq + 1 at position z0 + k P)
+    const auto f_cells = [&](const FView& fv, int k, float2*& c0, float2*& c1) {
+        if constexpr (LIT) {
+            const unsigned b = (((unsigned)fv.row | (unsigned)fv.slot) << 3) ^ ((unsigned)swz_c(k * P) << 3);
+            c0 = &at(b);
+            c1 = &at(b + pitch * 8);
+        } else {
+            const int c = fv.row + (fv.slot ^ swz_c(k * P));
+            c0 = tile + c;
+            c1 = tile + c + pitch;
+        }
+    };
     float4 pre[NPA];
     auto load_S = [&](int t) {
         const int pl = t / ytiles, ty = t - pl * ytiles, plane = d.xk0 + pl;  // (tiles of the planes xk0 ..: all, or a chunk)
         const FView fv = f_view();
         const float4* sp = reinterpret_cast<const float4*>(S) + (size_t)plane * L * ZR + (size_t)ty * TL + fv.off;
 #pragma unroll
-        for (int k = 0; k < NPA; ++k) pre[k] = (fv.z0 + k * P < d.z_in_hi) ? sp[(size_t)(k * P) * ZR] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        for (int k = 0; k < NPA; ++k) pre[k] = (FULLZ || fv.z0 + k * P < d.z_in_hi) ? sp[(size_t)(k * P) * ZR] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     };
     using TW = TwLds<LZ2, R3>;
     float2* twl = tile + 2 * TL * pitch;
@@ -765,20 +790,25 @@ __global__ __launch_bounds__(NT, (NT == 512 && (R3 << LZ2) > 576) ? 2 : kWavesXZ
                 butterflies<TOPR, TOPS, false>(u, twl + tw_off(LZ2, TOPS), fv.z0);
 #pragma unroll
                 for (int k = 0; k < NPA; ++k) {
-                    const int c = fv.row + (fv.slot ^ swz_c(k * P));
-                    tile[c] = v[k];
-                    tile[c + pitch] = u[k];
+                    float2 *c0, *c1;
+                    f_cells(fv, k, c0, c1);
+                    *c0 = v[k];
+                    *c1 = u[k];
                 }
             } else {
 #pragma unroll
             for (int k = 0; k < NPA; ++k) {
-                const int c = fv.row + (fv.slot ^ swz_c(k * P));
-                tile[c] = make_float2(pre[k].x, pre[k].y);
-                tile[c + pitch] = make_float2(pre[k].z, pre[k].w);
+                float2 *c0, *c1;
+                f_cells(fv, k, c0, c1);
+                *c0 = make_float2(pre[k].x, pre[k].y);
+                *c1 = make_float2(pre[k].z, pre[k].w);
             }
             }
         }
         const size_t g0 = ((size_t)plane * M + py0) * L;
+        // exp(-2 pi i xk / Nx), Nx = 2 Hx, of the point-wise step: a uniform load, requested a transform ahead (k_plane_twiddles evaluates
+        // the expression this step used to, per tile and wave)
+        const float2 wx = wxt[plane];
         float4 gv[REALG ? 1 : NPG];
         float2 gr[REALG ? NPG : 1];
         float2 ph_xy = make_float2(1.0f, 0.0f);
@@ -794,6 +824,21 @@ __global__ __launch_bounds__(NT, (NT == 512 && (R3 << LZ2) > 576) ? 2 : kWavesXZ
                 const float4* bp = ro.fb + ((size_t)plane * M + py0 + line) * 2;
                 b_a = bp[0];
                 b_b = bp[1];
+                if constexpr (R3 == 1 && WP && NPG >= 2) {
+                    // frequency of position lane + 64 k: (brev6(lane) << (LZ2 - 6)) | brev(k) -- the NPG entries of a lane are neighbours
+                    // behind one lane base (16-byte aligned: real_otf_args), taken as float4 and handed out in bit-reversed order
+                    constexpr int KB = LZ2 - 6;
+                    const float4* rp = reinterpret_cast<const float4*>(ro.ph_z + ((int)brev_n((unsigned)(tid & 63), 6) << KB));
+                    float4 blk[NPG / 2];
+#pragma unroll
+                    for (int q = 0; q < NPG / 2; ++q) blk[q] = rp[q];
+#pragma unroll
+                    for (int k = 0; k < NPG; ++k) {
+                        const int f = bit_rev(k, KB);
+                        gr[k] = (f & 1) ? make_float2(blk[f / 2].z, blk[f / 2].w) : make_float2(blk[f / 2].x, blk[f / 2].y);
+                    }
+                    return;
+                }
 #pragma unroll
                 for (int k = 0; k < NPG; ++k) gr[k] = ro.ph_z[pos2freq(p0 + (tid & 63) + 64 * k, LZ2, R3)];
                 return;
@@ -815,16 +860,13 @@ __global__ __launch_bounds__(NT, (NT == 512 && (R3 << LZ2) > 576) ? 2 : kWavesXZ
         }
         if (R3 == 9) load_G();
         if constexpr (LATE_G) {
-            lds_fft<LZ2, false, NT, R3, 0, 4>(tile, 2 * TL * R3, pitch, hp, true, twl);
+            lds_fft<LZ2, false, NT, R3, 0, 4, 0, LIT>(tile, 2 * TL * R3, pitch, hp, true, twl);
             load_G();
-            lds_fft<LZ2, false, NT, R3, 4, LZ2>(tile, 2 * TL * R3, pitch, hp, true, twl);
+            lds_fft<LZ2, false, NT, R3, 4, LZ2, 0, LIT>(tile, 2 * TL * R3, pitch, hp, true, twl);
         } else {
-            lds_fft<LZ2, false, NT, R3, TOPREG ? TOPR : 0>(tile, 2 * TL * R3, pitch, hp, true, twl);
+            lds_fft<LZ2, false, NT, R3, TOPREG ? TOPR : 0, LZ2, 0, LIT>(tile, 2 * TL * R3, pitch, hp, true, twl);
         }
         if constexpr (!WP) lds_barrier();
-        float sw, cw;
-        sincospif(-2.0f * (float)plane / (float)(2 * Hx), &sw, &cw);  // exp(-2 pi i xk / Nx), Nx = 2 Hx
-        const float2 wx = make_float2(cw, sw);
         {
             const int tid = launder(threadIdx.x);
             const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -838,17 +880,19 @@ __global__ __launch_bounds__(NT, (NT == 512 && (R3 << LZ2) > 576) ? 2 : kWavesXZ
 #pragma unroll
             for (int k = 0; k < NPG; ++k) {
                 const int hb = 64 * k + p0;  // the position bits above the lane's six
-                const int cA = line * pitch + (pA ^ swz_c(hb));
-                int cB;
-                if constexpr (R3 == 1) {
+                float2 *qA, *qB;
+                if constexpr (LIT) {  // (byte offsets: the rows' bases OR-ed into the lane constants, one XOR of a literal per cell)
                     const int flo = (int)brev_n((unsigned)hb, LZ2);
                     const int mhi = flo ? (int)brev_n((unsigned)((1 << (LZ2 - 6)) - flo), LZ2) : 0;
-                    cB = (TL + line) * pitch + (flo ? (pB1 ^ swz_c(mhi)) : pB0);
+                    const unsigned rA = (unsigned)(line * pitch), rB = (unsigned)((TL + line) * pitch);
+                    qA = &at(((rA | (unsigned)pA) << 3) ^ ((unsigned)swz_c(hb) << 3));
+                    qB = &at(flo ? ((rB | (unsigned)pB1) << 3) ^ ((unsigned)swz_c(mhi) << 3) : (rB | (unsigned)pB0) << 3);
                 } else {  // (3 * 2^a, 9 * 2^a: the mirror map is not XOR-linear)
-                    cB = (TL + line) * pitch + (phys(mirror_pos(lane + hb, L, LZ2, R3)) ^ rmask(TL + line, hp));
+                    qA = tile + line * pitch + (pA ^ swz_c(hb));
+                    qB = tile + (TL + line) * pitch + (phys(mirror_pos(lane + hb, L, LZ2, R3)) ^ rmask(TL + line, hp));
                 }
-                const float2 a = tile[cA];
-                const float2 bc = cconj(tile[cB]);
+                const float2 a = *qA;
+                const float2 bc = cconj(*qB);
                 const float2 E = make_float2(0.5f * (a.x + bc.x), 0.5f * (a.y + bc.y));
                 const float2 dlt = csub(a, bc);
                 const float2 O = make_float2(0.5f * dlt.y, -0.5f * dlt.x);
@@ -879,8 +923,8 @@ __global__ __launch_bounds__(NT, (NT == 512 && (R3 << LZ2) > 576) ? 2 : kWavesXZ
                 const float2 E2 = make_float2(0.5f * (Ya.x + Yb.x), 0.5f * (Ya.y + Yb.y));
                 const float2 dY = csub(Ya, Yb);
                 const float2 O2 = cmulc(make_float2(0.5f * dY.x, 0.5f * dY.y), wx);
-                tile[cA] = make_float2(E2.x - O2.y, E2.y + O2.x);
-                tile[cB] = make_float2(E2.x + O2.y, O2.x - E2.y);
+                *qA = make_float2(E2.x - O2.y, E2.y + O2.x);
+                *qB = make_float2(E2.x + O2.y, O2.x - E2.y);
             }
         }
         // (requesting them right after the fill, a whole tile ahead, gains nothing with two work-groups per CU: 4.72 vs 4.68 ms; with
@@ -891,7 +935,7 @@ __global__ __launch_bounds__(NT, (NT == 512 && (R3 << LZ2) > 576) ? 2 : kWavesXZ
         if (R3 != 9 && tn < ntiles) load_S(tn);
         if constexpr (WP) wave_lds_fence();
         else lds_barrier();
-        lds_fft<LZ2, true, NT, R3, 0, TOPREG ? TOPS : LZ2>(tile, 2 * TL * R3, pitch, hp, true, twl);
+        lds_fft<LZ2, true, NT, R3, 0, TOPREG ? TOPS : LZ2, 0, LIT>(tile, 2 * TL * R3, pitch, hp, true, twl);
         if constexpr (R3 > 1) {
             radix3_stage<R3, true, NT>(tile, 2 * TL, pitch, hp, true, 1 << LZ2, twl + TW::r3);
             wave_lds_fence();
@@ -905,9 +949,10 @@ __global__ __launch_bounds__(NT, (NT == 512 && (R3 << LZ2) > 576) ? 2 : kWavesXZ
             for (int k = 0; k < NPA; ++k) {
                 const int zk = fv.z0 + k * P;
                 if constexpr (!TOPREG) {
-                if (zk >= d.z_out_lo && zk < d.z_out_hi) {
-                    const int c = fv.row + (fv.slot ^ swz_c(k * P));
-                    const float2 a0 = tile[c], a1 = tile[c + pitch];
+                if (FULLZ || (zk >= d.z_out_lo && zk < d.z_out_hi)) {
+                    float2 *c0, *c1;
+                    f_cells(fv, k, c0, c1);
+                    const float2 a0 = *c0, a1 = *c1;
                     dp[(size_t)(k * P) * ZR] = make_float4(a0.x, a0.y, a1.x, a1.y);
                 }
                 }
@@ -916,16 +961,17 @@ __global__ __launch_bounds__(NT, (NT == 512 && (R3 << LZ2) > 576) ? 2 : kWavesXZ
                 float2 v[NPA], u[NPA];
 #pragma unroll
                 for (int k = 0; k < NPA; ++k) {
-                    const int c = fv.row + (fv.slot ^ swz_c(k * P));
-                    v[k] = tile[c];
-                    u[k] = tile[c + pitch];
+                    float2 *c0, *c1;
+                    f_cells(fv, k, c0, c1);
+                    v[k] = *c0;
+                    u[k] = *c1;
                 }
                 butterflies<TOPR, TOPS, true>(v, twl + tw_off(LZ2, TOPS), fv.z0);
                 butterflies<TOPR, TOPS, true>(u, twl + tw_off(LZ2, TOPS), fv.z0);
 #pragma unroll
                 for (int k = 0; k < NPA; ++k) {
                     const int zk = fv.z0 + k * P;
-                    if (zk >= d.z_out_lo && zk < d.z_out_hi) dp[(size_t)(k * P) * ZR] = make_float4(v[k].x, v[k].y, u[k].x, u[k].y);
+                    if (FULLZ || (zk >= d.z_out_lo && zk < d.z_out_hi)) dp[(size_t)(k * P) * ZR] = make_float4(v[k].x, v[k].y, u[k].x, u[k].y);
                 }
             }
         }
@@ -934,6 +980,16 @@ __global__ __launch_bounds__(NT, (NT == 512 && (R3 << LZ2) > 576) ? 2 : kWavesXZ
         t = tn;
         tn = dyn ? __builtin_amdgcn_readfirstlane(s_next_tile) : tn + (int)gridDim.x;
     }
+}
+
+// exp(-2 pi i xk / Nx), Nx = 2 Hx, for xk <= Hx/2: the plane twiddle of the point-wise step of k_z_pair_pipe, evaluated on the device
+// by the expression the other z kernels evaluate per tile, so that the paired pass reads the bits it used to compute
+__global__ __launch_bounds__(256) void k_plane_twiddles(float2* __restrict__ wxt, int Hx) {
+    const int plane = blockIdx.x * blockDim.x + threadIdx.x;
+    if (plane > Hx / 2) return;
+    float sw, cw;
+    sincospif(-2.0f * (float)plane / (float)(2 * Hx), &sw, &cw);
+    wxt[plane] = make_float2(cw, sw);
 }
 
 // Complex pair OTF -> real pair OTF: Gr = Re(G * conj(P)) with P the phase ramp of the PSF centre's offset; the largest
@@ -957,12 +1013,13 @@ __global__ __launch_bounds__(256) void k_g_to_real(const float4* __restrict__ G,
     atomicMax(&stats[1], __float_as_uint(max_re));
 }
 
-// the real OTF of a slot and its phase tables ([xk <= Hx/2][ky][kz] behind each other in `ph`)
+// the real OTF of a slot and its phase tables ([xk <= Hx/2, rounded up to an even count][ky][kz] behind each other in `ph`)
+constexpr int ph_x_entries(int hx) { return (hx / 2 + 2) & ~1; }
 RealOtf real_otf_args(const NativeFft& f, bool adj_slot) {
     RealOtf ro{};
     ro.g = adj_slot ? f.Gr_adj.as<float2>() : f.Gr.as<float2>();
     ro.ph_x = f.ph.as<float2>();
-    ro.ph_y = ro.ph_x + (f.dims.hx / 2 + 1);
+    ro.ph_y = ro.ph_x + ph_x_entries(f.dims.hx);  // (an even count, and y is even: the z table starts on 16 bytes, k_z_pair_pipe reads it as float4)
     ro.ph_z = ro.ph_y + f.dims.ny;
     if (f.otf_factored()) {
         ro.fa = adj_slot ? f.Gf_adj.as<float4>() : f.Gf.as<float4>();
@@ -1029,6 +1086,13 @@ int z_pair_case(const NativeDims& d, F&& f) {
 
 }  // namespace
 
+// the table of plane twiddles behind the axis twiddles (init)
+int NativeFft::fill_plane_twiddles(hipStream_t s, float2* dst) {
+    tw_plane = dst;
+    hipLaunchKernelGGL(k_plane_twiddles, dim3((unsigned)((dims.hx / 2 + 1 + 255) / 256)), dim3(256), 0, s, dst, dims.hx);
+    return launch_check("k_plane_twiddles");
+}
+
 int NativeFft::y_pass(hipStream_t s, bool inverse, YRoute route, const float2* src_o, float2* dst_o, int xk0, int xkn) {
     const int Hx = dims.hx, L = dims.nz;
     if (xkn < 0) xkn = Hx / 2 + 1;
@@ -1077,10 +1141,10 @@ int NativeFft::z_conv(hipStream_t s, bool conj_otf, const float2* src_o, float2*
         case ZRoute::pair_pipe:
         case ZRoute::pair_pipe_real: {
             const int ntiles = xkn * (M / kPairLines);
-            bool phl = true;  // (576-point lines have no LDS phase table: MI_ZQ_CASES)
-            z_pair_takes(dims.lz2, dims.r3z, nullptr, &phl);
             const bool fact = real_otf && otf_factored();  // (the A_r table in place of the z ramp's: z_pair_factored)
-            const size_t lds = lds_bytes(2 * kPairLines, L) + (fact ? sizeof(float4) * (size_t)L : real_otf && phl ? sizeof(float2) * (size_t)L : 0);
+            const bool full = z_full_grid(d, sw);
+            // (576-point lines have no LDS phase table: MI_ZQ_CASES.)  The kernel holds these bytes as a static array: no dynamic LDS
+            const size_t lds = z_pair_lds(dims.lz2, dims.r3z, real_otf, fact);
             const int per_cu = std::max(1, std::min(2, (int)(kLdsOneWg / lds)));  // 8 waves of 128 registers each: two fit a CU
             const unsigned grid = (unsigned)std::min(ntiles, per_cu * n_cu);
             int* ctr_p = nullptr;
@@ -1092,15 +1156,20 @@ int NativeFft::z_conv(hipStream_t s, bool conj_otf, const float2* src_o, float2*
             return z_pair_case(dims, [&](auto lg, auto r, auto nth, auto ph_lds) {
                 constexpr int LG = lg(), R = r(), NTH = nth();
                 constexpr bool PH = ph_lds();
+                const auto go = [&](auto kernel, const char* name) {
+                    return launch_lds(kernel, grid, NTH, 0, s, name, Tp, Sp, Gp, d, twz, cj, ntiles, ro, ctr_p, tw_plane);
+                };
+                // every form of the OTF with and without the plane bounds of a pruned grid (z_full_grid)
                 if constexpr (z_pair_factored(LG, R)) {
                     if (fact)
-                        return launch_lds(k_z_pair_pipe<LG, R, true, NTH, kPairLines, PH, true, true>, grid, NTH, lds, s, "k_z_pair_pipe<factored OTF>",
-                                          Tp, Sp, Gp, d, twz, cj, ntiles, ro, ctr_p);
+                        return full ? go(k_z_pair_pipe<LG, R, true, NTH, kPairLines, PH, true, true, true>, "k_z_pair_pipe<factored OTF, full grid>")
+                                    : go(k_z_pair_pipe<LG, R, true, NTH, kPairLines, PH, true, true, false>, "k_z_pair_pipe<factored OTF>");
                 }
-                return real_otf ? launch_lds(k_z_pair_pipe<LG, R, true, NTH, kPairLines, PH>, grid, NTH, lds, s, "k_z_pair_pipe<real OTF>", Tp, Sp, Gp,
-                                             d, twz, cj, ntiles, ro, ctr_p)
-                                : launch_lds(k_z_pair_pipe<LG, R, false, NTH, kPairLines, PH>, grid, NTH, lds, s, "k_z_pair_pipe", Tp, Sp, Gp, d,
-                                             twz, cj, ntiles, ro, ctr_p);
+                if (real_otf)
+                    return full ? go(k_z_pair_pipe<LG, R, true, NTH, kPairLines, PH, true, false, true>, "k_z_pair_pipe<real OTF, full grid>")
+                                : go(k_z_pair_pipe<LG, R, true, NTH, kPairLines, PH, true, false, false>, "k_z_pair_pipe<real OTF>");
+                return full ? go(k_z_pair_pipe<LG, R, false, NTH, kPairLines, PH, true, false, true>, "k_z_pair_pipe<full grid>")
+                            : go(k_z_pair_pipe<LG, R, false, NTH, kPairLines, PH, true, false, false>, "k_z_pair_pipe");
             });
         }
         case ZRoute::conv_pipe:
@@ -1133,7 +1202,9 @@ int NativeFft::try_real_otf(hipStream_t s, const int delta[3]) {
     if (!real_otf_possible(dims, sw)) return MI_OK;
     // phase tables exp(-2 pi i (k delta mod F) / F) in double on the host: x by xk <= Hx/2 (F = 2 Hx), y by ky, z by kz
     const int nx = Hx / 2 + 1;
-    std::vector<float2> h((size_t)nx + M + L);
+    const int nxp = ph_x_entries(Hx);
+    MI_REQUIRE(M % 2 == 0, "native FFT: odd y length %d", M);  // (the z table must start on 16 bytes)
+    std::vector<float2> h((size_t)nxp + M + L, make_float2(1.0f, 0.0f));
     const double two_pi = 6.283185307179586476925286766559;
     auto fill = [&](float2* dst, int n, long long F, int dl) {
         for (int k = 0; k < n; ++k) {
@@ -1142,8 +1213,8 @@ int NativeFft::try_real_otf(hipStream_t s, const int delta[3]) {
         }
     };
     fill(h.data(), nx, 2LL * Hx, delta[0]);
-    fill(h.data() + nx, M, M, delta[1]);
-    fill(h.data() + nx + M, L, L, delta[2]);
+    fill(h.data() + nxp, M, M, delta[1]);
+    fill(h.data() + nxp + M, L, L, delta[2]);
     MI_TRY(ph.alloc(sizeof(float2) * h.size()));
     MI_HIP(hipMemcpyAsync(ph.p, h.data(), sizeof(float2) * h.size(), hipMemcpyHostToDevice, s));
     const RealOtf ro = real_otf_args(*this, false);  // (k_g_to_real reads the phase tables only)

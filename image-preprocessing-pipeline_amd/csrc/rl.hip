@@ -358,6 +358,7 @@ extern "C" int mi_rl_fft_route(mi_rl_ctx* ctx, mi_fft_route* out) {
     out->ty = f.dims.ty;
     out->tc = f.dims.tc;
     out->tl = f.dims.tl;
+    out->z_full_grid = z_full_grid(f.dims, f.sw) ? 1 : 0;
     return MI_OK;
 }
 

@@ -395,10 +395,19 @@ class RLContext:
     @property
     def fft_route(self) -> dict:
         """What the context's FFT plan does (``mi_rl_fft_route``): kernel family of the z pass, layouts, tile hand-out, tile sizes --
-        decided from the environment at the moment the context was created."""
+        decided from the environment at the moment the context was created.  (The twelve decisions between kernel families and tile
+        sizes; the form the paired z kernel runs in is ``z_full_grid``.)"""
         r = capi.FftRoute()
         check(lib().mi_rl_fft_route(self._h, C.byref(r)))
-        return {name: int(getattr(r, name)) for name, _ in capi.FftRoute._fields_}
+        return {name: int(getattr(r, name)) for name, _ in capi.FftRoute._fields_ if name != "z_full_grid"}
+
+    @property
+    def z_full_grid(self) -> bool:
+        """The paired z pass runs without plane bounds on its loads and stores (last field of ``mi_fft_route``): every z plane of the
+        grid is read and written.  False on a pruned padded grid and under ``MI_FFT_Z_GENERAL=1``."""
+        r = capi.FftRoute()
+        check(lib().mi_rl_fft_route(self._h, C.byref(r)))
+        return bool(r.z_full_grid)
 
     @property
     def spectrum_row_floats(self) -> int:

@@ -183,9 +183,10 @@ int mi_rl_otf_form(mi_rl_ctx* ctx, int* rank, int* rank_adj);
  * whole, aligned fused x pass runs as the persistent kernel; x_splits 1 = ... and can run a subset of its tiles (mi_rl_fuses == 2);
  * x_dynamic / z_dynamic 1 = the persistent x launches / the paired z pass take their tiles from a device counter (MI_X_DYN /
  * MI_Z_DYN = 0: at a fixed stride); pruned 1 = the passes skip what a padded grid leaves empty; ty, tc, tl: rows, columns and lines
- * of the x, y and z tiles. */
+ * of the x, y and z tiles; z_full_grid 1 = k_z_pair_pipe runs without plane bounds on its loads and stores (every z plane of the grid
+ * is read and written; MI_FFT_Z_GENERAL=1 or a pruned padded grid: 0). */
 typedef struct {
-    int native, paired, z_kernel, real_otf, x_pipelined, x_splits, x_dynamic, z_dynamic, pruned, ty, tc, tl;
+    int native, paired, z_kernel, real_otf, x_pipelined, x_splits, x_dynamic, z_dynamic, pruned, ty, tc, tl, z_full_grid;
 } mi_fft_route;
 int mi_rl_fft_route(mi_rl_ctx* ctx, mi_fft_route* out);
 int mi_rl_sharded_begin(mi_rl_ctx* ctx, void* stream, const float* bl);
