@@ -32,7 +32,8 @@ Departures from the reference:
   * when no preprocessing is asked for, the stitch reads the source folder;
   * ``--nthreads``, ``--timeout``, ``--vram_mem_fraction_gpu0`` and ``--enable_axis_correction`` are accepted and ignored.
 Refused by name: ``--imaris`` (NotImplementedError, before anything is created) and a run under ``WORLD_SIZE`` > 1 (RuntimeError: the
-stages' rank modes are not composed here).  A stage's own refusal propagates unchanged.
+stages' rank modes are not composed here).  A stage's own refusal propagates unchanged: of ``--padding_mode`` the per-slice filter
+does every choice but ``empty``.
 """
 from __future__ import annotations
 

@@ -21,7 +21,10 @@ NORTH_SOUTH, WEST_EAST = 0, 1
 SINBLEND, NOBLEND = 0, 1   # mi_blending (include/mi_stitch.h)
 HALVE_MEAN, HALVE_MAX = 0, 1   # mi_halve_method (include/mi_pyramid.h)
 PS_U8, PS_U16, PS_F32 = 0, 1, 2   # mi_pystripe_dtype (include/mi_pystripe.h)
-PS_PADDING = {"reflect": 0, "wrap": 1, "symmetric": 2, "edge": 3}   # mi_pystripe_padding
+# mi_pystripe_padding: four index maps, then the value modes (PS_VALUE_PADDING; the Python layer takes them with extended=True)
+PS_PADDING = {"reflect": 0, "wrap": 1, "symmetric": 2, "edge": 3, "constant": 4, "linear_ramp": 5, "maximum": 6, "mean": 7, "median": 8,
+              "minimum": 9}
+PS_VALUE_PADDING = ("constant", "linear_ramp", "maximum", "mean", "median", "minimum")
 PS_DOWN = {"max": 0, "min": 1, "mean": 2, "median": 3}   # mi_pystripe_down
 PS_MEDIAN_MAX_BLOCK = 64  # MI_PS_MEDIAN_MAX_BLOCK
 PS_NOTCH_ROUTE = ("pass", "level", "axis", "n", "kp", "kb", "R", "threads", "lds")   # a record of mi_pystripe_plan_notch_routes
@@ -84,6 +87,7 @@ class PystripeParams(C.Structure):
 PS_MAX_LEVELS = 24  # MI_PS_MAX_LEVELS
 PS_MAX_TAPS = 128  # MI_PS_MAX_TAPS
 PS_BLEACH_LDS_ROW = 20436  # MI_PS_BLEACH_LDS_ROW
+PS_PAD_LDS_LINE = 9968  # MI_PS_PAD_LDS_LINE
 
 
 class PystripeInfo(C.Structure):

@@ -16,6 +16,7 @@ The clips go through as given, in log1p units, and ``bleach_correction_clip_med`
 device (four-class multi-Otsu of the log image).  With the reference's defaults of 20 and 255 that estimate lies below clip_min
 and the assert of correct_bleaching fires, here as there: give clips in log1p units.
 
+``--padding-mode`` takes every mode of ``numpy.pad`` but ``empty`` (the per-slice filter runs with ``extended=True``).
 Additions and refusals: a project ``.xml`` as ``--input`` is opened as ``ipp_amd.tsv.TSVVolume`` (the reference hands
 the path itself to a function that rejects it).  Refused by name before any folder is made: ``--imaris``, ``--fnt``, ``--movie``, an
 ``.ims`` input, ``--channel`` other than 0 together with ``--teraFly``.  ``--nthreads``, ``--timeout``, ``--needed-memory`` and
@@ -53,7 +54,7 @@ def make_parser():
     p.add_argument("--channel", "-c", type=int, default=0, help="channel of RGB slices; negative: the slices are copied unprocessed")
     p.add_argument("--gaussian", "-g", help="accepted; does nothing, as in the reference's process_img", **flag)
     p.add_argument("--destripe", help="stripe filter at sigma (250, 250), bidirectional", **flag)
-    p.add_argument("--padding-mode", "-w", type=str, default="reflect", help="padding of the stripe filter: reflect, wrap, symmetric, edge")
+    p.add_argument("--padding-mode", "-w", type=str, default="reflect", help="padding of the stripe filter: reflect, wrap, symmetric, edge, constant, linear_ramp, maximum, mean, median, minimum")
     p.add_argument("--downsample-x", "-dsx", type=int, default=0, help="2-D down-sampling factor along x")
     p.add_argument("--downsample-y", "-dsy", type=int, default=0, help="2-D down-sampling factor along y")
     p.add_argument("--downsample-method", "-dsm", type=str, default="mean", help="max, min, mean or median")

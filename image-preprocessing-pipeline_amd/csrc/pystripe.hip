@@ -154,7 +154,11 @@ int derive(int ny_in, int nx_in, int in_dtype, const mi_pystripe_params& q, int 
     MI_REQUIRE(q.sigma1 >= 0 && q.sigma2 >= 0, "mi_pystripe: sigma (%g, %g) is negative", q.sigma1, q.sigma2);
     P.filter = q.sigma1 > 0 || q.sigma2 > 0;
     MI_REQUIRE(!P.filter || (q.sigma1 > 0 && q.sigma2 > 0), "np_notch: sigma must be positive (sigma = (%g, %g))", q.sigma1, q.sigma2);
-    MI_REQUIRE(q.padding_mode >= MI_PS_REFLECT && q.padding_mode <= MI_PS_EDGE, "mi_pystripe: padding_mode %d", q.padding_mode);
+    MI_REQUIRE(q.padding_mode >= MI_PS_REFLECT && q.padding_mode <= MI_PS_MINIMUM, "mi_pystripe: padding_mode %d", q.padding_mode);
+    // constant padding takes its value from bleach_clip_min also without a frequency: log1p of it (NaN with a frequency: per tile)
+    MI_REQUIRE(q.padding_mode != MI_PS_CONSTANT || q.bleach_frequency != 0 || (std::isfinite(q.bleach_clip_min) && q.bleach_clip_min >= 0),
+               "mi_pystripe: padding_mode constant pads with log1p(bleach_clip_min); bleach_clip_min %g is not a finite value of 0 or more",
+               q.bleach_clip_min);
     MI_REQUIRE(q.down_method >= MI_PS_DOWN_MAX && q.down_method <= MI_PS_DOWN_MEDIAN, "mi_pystripe: down_method %d", q.down_method);
     MI_REQUIRE(q.down_y >= 0 && q.down_x >= 0 && (q.down_y > 0) == (q.down_x > 0), "mi_pystripe: down_sample (%d, %d)", q.down_y, q.down_x);
     MI_REQUIRE(q.rotate == 0 || q.rotate == 90 || q.rotate == 180 || q.rotate == 270, "mi_pystripe: rotate %d (0, 90, 180, 270)", q.rotate);
@@ -239,7 +243,17 @@ int derive(int ny_in, int nx_in, int in_dtype, const mi_pystripe_params& q, int 
             // m = (n + L - 1) / 2 with n >= 1
             MI_REQUIRE(P.h[l] >= L / 2 && P.w[l] >= L / 2, "mi_pystripe: level %d has %d x %d coefficients", l, P.h[l], P.w[l]);
         }
-        if (P.passes == 2 && I.levels) { P.sz_P = (size_t)P.h[0] * P.w[0]; P.off_P = take(P.sz_P); }
+        // a value padding mode writes the padded image before the first level; an index map never does
+        P.valpad = I.levels && q.padding_mode >= MI_PS_CONSTANT;
+        if ((P.passes == 2 || P.valpad) && I.levels) { P.sz_P = (size_t)P.h[0] * P.w[0]; P.off_P = take(P.sz_P); }
+        if (P.valpad) {
+            const int m = q.padding_mode;
+            if (m == MI_PS_CONSTANT) P.sz_pvec = (au & MI_PS_AUTO_MIN) ? 1 : 0;
+            else if (m != MI_PS_LINEAR_RAMP) P.sz_pvec = (size_t)I.ny + I.nx + 1;
+            if (m == MI_PS_MAXIMUM || m == MI_PS_MINIMUM || m == MI_PS_MEAN) P.sz_ppart = 2 * (size_t)I.ny * cdiv(I.nx, 64);
+            if (P.sz_pvec) P.off_pvec = take(P.sz_pvec);
+            if (P.sz_ppart) P.off_ppart = take(P.sz_ppart);
+        }
         // L / H of a level's analysis (h[l - 1] rows of w[l]); lo1 / hi1 of its synthesis (2 h[l] - L + 2 <= h[l - 1] + 1 rows).  The
         // first level is the largest while the extents are L - 1 or more; an explicit level on a shorter extent n GROWS it towards
         // L - 1 ((n + L - 1) / 2 > n), so the largest level is looked for.
@@ -374,11 +388,13 @@ int run_chunk(Plan& P, hipStream_t st, const void* in, const float* flat, void* 
         kL.clip_status = nullptr;
     }
     const int Lv = I.levels;
+    if (P.valpad) MI_TRY(run_value_pad(P, st, src, cnt));
     for (int pass = 0; pass < P.passes; ++pass) {
-        // analysis: of the tile through its padding map, of the padded image the first pass left, or of the level above
+        // analysis: of the tile through its padding map, of the padded image (a value mode's, or the one the first pass left), or of
+        // the level above
         for (int l = 1; l <= Lv; ++l) {
             Src s;
-            if (l == 1 && pass == 0) {
+            if (l == 1 && pass == 0 && !P.valpad) {
                 s = src;
                 s.pad = I.base_pad; s.mode = q.padding_mode; s.logp = 1;
             } else if (l == 1) {

@@ -85,9 +85,11 @@ __global__ void __launch_bounds__(256) auto_hist_kernel(Src s, const float* tabl
 // The triple and the status of every tile: given clips keep their slot, an estimated one is the float32 centre of the bin the search
 // named; min is raised to log1p(1); the asserts of correct_bleaching :524-528 on the result.  A tile without usable clips is zeroed
 // through `varies`; its estimated slots hold NaN unless the order check failed (the triple is then what the caller reports).
+// padc (constant padding with an estimated minimum, else null): log1p of the minimum BEFORE it is raised, per tile at stride
+// padc_ts -- filter_streaks :1101-1105 pads with log1p of the threshold itself; 0 for a tile without usable clips (it is zeroed).
 __global__ void __launch_bounds__(64) auto_clips_kernel(int cnt, int bits, float gmin, float gmed, float gmax, double floor_lo, const float* edges,
                                                         const int* indices, const int* otsu_status, const int* nonfinite, int uniform_rule,
-                                                        int* varies, float* clips, int* status) {
+                                                        int* varies, float* clips, int* status, float* padc, i64 padc_ts) {
     const int tile = blockIdx.x * 64 + threadIdx.x;
     if (tile >= cnt) return;
     float c[3] = {gmin, gmed, gmax};
@@ -102,6 +104,7 @@ __global__ void __launch_bounds__(64) auto_clips_kernel(int cnt, int bits, float
             c[k] = st == MI_PS_CLIPS_OK ? (e[i] + e[i + 1]) / 2.0f : NAN;
         }
     if (st == MI_PS_CLIPS_OK && !(c[0] >= 0.f && c[1] > c[0] && c[2] > c[0] && c[2] > c[1])) st = MI_PS_CLIPS_ORDER;
+    if (padc) padc[tile * padc_ts] = st == MI_PS_CLIPS_OK ? (float)log1p((double)c[0]) : 0.f;
     if (st == MI_PS_CLIPS_OK) c[0] = (float)fmax((double)c[0], floor_lo);
     if (st > 0) varies[tile] = 0;
     clips[3 * tile] = c[0]; clips[3 * tile + 1] = c[1]; clips[3 * tile + 2] = c[2];
@@ -148,9 +151,10 @@ int run_auto_clips(const Plan& P, hipStream_t st, Src src, int cnt, int* varies,
     hipLaunchKernelGGL(auto_hist_kernel, grid, dim3(256), 0, st, src, table, P.ncodes, edges, nonfinite, counts);
     MI_TRY(launch_check("auto_hist_kernel"));
     MI_TRY(multiotsu_launch(st, counts, cnt, MI_OTSU_MAX_CLASSES, indices, nvalues, otsu_status, work));
+    float* padc = P.valpad && q.padding_mode == MI_PS_CONSTANT && (P.au & MI_PS_AUTO_MIN) ? P.buf(P.off_pvec) : nullptr;
     hipLaunchKernelGGL(auto_clips_kernel, dim3(cdiv((size_t)cnt, 64)), dim3(64), 0, st, cnt, P.au, (float)q.bleach_clip_min,
                        (float)q.bleach_clip_med, (float)q.bleach_clip_max, std::log1p(1.0), edges, indices, otsu_status, nonfinite,
-                       !q.keep_uniform && !q.log_output, varies, clips, status);
+                       !q.keep_uniform && !q.log_output, varies, clips, status, padc, (i64)P.sz_pvec);
     return launch_check("auto_clips_kernel");
 }
 

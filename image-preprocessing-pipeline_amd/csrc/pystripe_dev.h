@@ -17,7 +17,7 @@ using histdev::float_key;   // order-preserving keys of floats
 using histdev::key_float;
 using i64 = long long;
 
-enum { MAP_IDENTITY = 4 };
+enum { MAP_IDENTITY = -1 };   // Src::mode beside the index maps of mi_pystripe_padding: the image is read as it lies
 enum { SRC_KEY = 3 };   // Src::dtype beside mi_pystripe_dtype: order-preserving keys of floats (float_key)
 enum { OUT_FLOAT = 0, OUT_TO8 = 1, OUT_CLIPCAST = 2 };
 

@@ -6,6 +6,9 @@
 //   load      (pystripe_wavelet.hip) the first analysis level reads the tile itself: integer load, log1p and the numpy.pad index map
 //             (reflect / wrap / symmetric / edge) are folded into its addressing, so the padded image is never written.  The row pass
 //             runs over the SOURCE rows only; the column pass looks rows up through the same map.
+//   pad       (pystripe_pad.hip) the value modes of numpy.pad (constant, linear_ramp, maximum, minimum, mean, median) are no index
+//             maps: the row and column statistics of the log image (one pass for max / min / mean, a radix selection per line for the
+//             median), their corner value, then the padded log image itself, which the first level reads as it lies.
 //   analysis  (pystripe_wavelet.hip) out[i] = sum_t F[t] in[sym(2 i + 1 - t)], floor((n + 17) / 2) coefficients ('symmetric', db9);
 //             rows then columns: L, H along axis -1, then A, cH (from L) and cV, cD (from H) along axis -2 -- cH is the high-pass along
 //             axis -2 of the low-pass along axis -1, PyWavelets' 'da'.
@@ -83,6 +86,10 @@ struct Plan {
     // vectors, rows first; the tile maximum; the forward result of lines too long for LDS (doubles, two floats each)
     size_t off_L = 0, off_F = 0, off_lmax = 0, off_key = 0, off_vec = 0, off_M = 0, off_fwd = 0;
     size_t sz_L = 0, sz_F = 0, sz_lmax = 0, sz_vec = 0, sz_fwd = 0;
+    // value padding (the padded image itself is P): [row statistics ny | column statistics nx | corner], or the tile's constant
+    // alone (log1p of its estimated clip_min); the row partials of the statistics pass (doubles, two floats each)
+    bool valpad = false;
+    size_t off_pvec = 0, off_ppart = 0, sz_pvec = 0, sz_ppart = 0;
     std::vector<NotchTab> tabs;   // [pass][level 1..L][axis 0: cH along -1, 1: cV along -2]
     DevBuf tw_buf, w_buf, scratch, varies;
     i64 cap = 0;
@@ -110,6 +117,9 @@ int launch_analysis(const Plan& P, hipStream_t st, int l, const Src& s, int cnt)
 int launch_synthesis(const Plan& P, hipStream_t st, int l, bool fin, const Sink& k, int cnt);
 // the four filters of the orthogonal wavelet with the reconstruction low-pass rec_lo[P.L], for the generic kernels
 int upload_filter_table(Plan& P, const double* rec_lo);
+
+// pystripe_pad.hip: a value padding mode (P.valpad): the padded log image of the cnt tiles behind `src` into the plan's P
+int run_value_pad(const Plan& P, hipStream_t st, Src src, int cnt);
 
 // pystripe_notch.hip: the tables of every (pass, level, axis), and the notch on nlines lines (element stride es, line stride ls)
 int build_tables(Plan& P);

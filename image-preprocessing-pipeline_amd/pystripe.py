@@ -12,7 +12,9 @@ an error.
 
 What is computed (reference line numbers in include/mi_pystripe.h): uniform tile -> zeros; flat field; ``down_sample`` (max / min /
 mean / median, zero-padded blocks like skimage's ``block_reduce``); ``filter_streaks`` = log1p, numpy padding (reflect / wrap / symmetric /
-edge), wavelet decomposition (``wavelet=``: 'db9', the pipeline's choice; 'haar' / 'db1' .. 'db20'; or any orthogonal wavelet of up
+edge as index maps of the first wavelet level; with ``extended=True`` also constant / linear_ramp / maximum / mean / median / minimum,
+for which the row and column statistics of the log image and the padded image itself are made on the device; the constant is 0 or
+log1p of ``bleach_correction_clip_min`` -- given, or the tile's own estimate), wavelet decomposition (``wavelet=``: 'db9', the pipeline's choice; 'haar' / 'db1' .. 'db20'; or any orthogonal wavelet of up
 to 128 taps as an object with ``rec_lo`` -- ``pywt.Wavelet("coif15")`` -- or the coefficients themselves; ``wavelets.py``), the
 packed-position Gaussian notch on cH (and cV when ``bidirectional``), reconstruction, crop,
 bleach correction (``bleach_correction_frequency`` with the three clips in log1p units, each given or, when None, estimated per tile
@@ -31,12 +33,13 @@ Departures, all stated in INTEGRATION.md:
     zeros for a uniform such tile and divides by zero otherwise);
   * ``extended=True`` (``process_img``, ``filter_streaks``, ``batch_filter``, ``make_params``; default False) opens what these entry
     points refused by name before it existed and still refuse without it: a frequency without all three clips (the missing ones are
-    then estimated per tile), ``down_sample_method='median'``, ``new_size`` in ``process_img``, a ``threshold``;
+    then estimated per tile), ``down_sample_method='median'``, ``new_size`` in ``process_img``, a ``threshold``, the six value modes
+    of ``padding_mode``;
   * refused by name also with it: ``enable_masking``, ``exclude_dark_edges_set_them_to_zero``,
     a ``new_size`` that needs skimage's Gaussian pre-filter (the tile
     shape below ``new_size`` as tuples with an axis that shrinks) or meets an integer tile with a float ``d_type``, ``.dcimg`` input,
     a median ``down_sample`` over blocks of more than 64 samples, a wavelet NAME without a built-in table (``'coif15'``: hand in
-    the coefficients instead), biorthogonal wavelets, other padding modes, a ``threshold`` of 0 or less with ``sigma1 == 0``
+    the coefficients instead), biorthogonal wavelets, ``padding_mode='empty'``, a ``threshold`` of 0 or less with ``sigma1 == 0``
     (a ``threshold`` above 0 has no effect: ``use_thresholding`` is never set on this path, nor has ``crossover``; 0 or less runs the
     single ``sigma1`` pass);
   * accepted and ignored: ``workers``, ``threads_per_gpu``, ``timeout``, ``gpu_semaphore``, ``z_step``, ``print_input_file_names``,
@@ -125,6 +128,15 @@ def _refuse(name, value, why):
     raise NotImplementedError(f"{name}={value!r}: {why}")
 
 
+def _check_padding(padding_mode, extended):
+    """Raises NotImplementedError for a mode of numpy.pad this build does not do: 'empty' always (the reference then filters
+    uninitialised memory), the six value modes without ``extended=True``."""
+    mode = padding_mode.lower() if isinstance(padding_mode, str) else padding_mode
+    if mode == "empty" or (mode in capi.PS_VALUE_PADDING and not extended):
+        _refuse("padding_mode", padding_mode, "reflect, wrap, symmetric and edge are built" if not extended else
+                "the reference pads with uninitialised memory; every other mode of numpy.pad is built")
+
+
 def _check_unsupported(kw):
     """Raises NotImplementedError naming the first option this build does not do.  Without ``extended=True`` that includes what the
     entry points refused before the option existed: a frequency without all three clips, ``new_size`` in ``process_img``, a
@@ -146,6 +158,8 @@ def _check_unsupported(kw):
         s1, s2 = _sigma_pair(kw["sigma"])
         if s1 == 0 and s2 != 0:
             _refuse("threshold", threshold, f"with sigma={kw['sigma']!r} the reference runs filter_subband at sigma 0; not built")
+    if "padding_mode" in kw and _sigma_pair(kw.get("sigma", (0, 0))) > (0, 0):
+        _check_padding(kw["padding_mode"], kw.get("extended"))
     if kw.get("log1p_normalization_needed") is False:
         _refuse("log1p_normalization_needed", False, "only the log1p path is built")
 
@@ -186,9 +200,10 @@ def check_bleach(shape, frequency, clip_min, clip_med, clip_max, max_method=Fals
 
 
 def _bleach_opts(shape, down_sample, frequency, max_method, clip_min, clip_med, clip_max):
-    """{} or the bleach keywords of make_params, after the checks that need no device."""
+    """The bleach keywords of make_params, after the checks that need no device.  Without a frequency only a given ``clip_min``
+    is kept: padding_mode='constant' pads with it whether or not the correction runs."""
     if frequency is None:
-        return {}
+        return {} if clip_min is None else dict(bleach_correction_clip_min=clip_min)
     check_bleach(shape, frequency, clip_min, clip_med, clip_max, max_method, down_sample)
     return dict(bleach_correction_frequency=frequency, bleach_correction_max_method=max_method, bleach_correction_clip_min=clip_min,
                 bleach_correction_clip_med=clip_med, bleach_correction_clip_max=clip_max)
@@ -225,7 +240,9 @@ def make_params(in_dtype, flat=False, down_sample=None, down_sample_method="max"
                 bleach_correction_frequency=None, bleach_correction_max_method=False, bleach_correction_clip_min=None,
                 bleach_correction_clip_med=None, bleach_correction_clip_max=None, extended=False):
     """mi_pystripe_params for process_img's options.  Everything the C side cannot name itself is refused here.  ``extended=True``
-    takes a clip that is None (NaN in the struct: estimated per tile) and the median down-sampling."""
+    takes a clip that is None (NaN in the struct: estimated per tile), the median down-sampling and the value modes of numpy.pad
+    (``padding_mode`` 'constant', 'linear_ramp', 'maximum', 'mean', 'median', 'minimum'; ``bleach_correction_clip_min`` is the constant's
+    source also without a frequency)."""
     s1, s2 = _sigma_pair(sigma)
     filt = (s1, s2) > (0, 0)
     wobj = None
@@ -234,9 +251,8 @@ def make_params(in_dtype, flat=False, down_sample=None, down_sample_method="max"
         if (s1 > 0) != (s2 > 0) or s1 < 0 or s2 < 0:
             raise ValueError(f"np_notch: sigma must be positive (sigma={sigma!r})")
         mode = padding_mode.lower() if isinstance(padding_mode, str) else padding_mode
+        _check_padding(padding_mode, extended)
         if mode not in capi.PS_PADDING:
-            if mode in ("constant", "linear_ramp", "maximum", "mean", "median", "minimum", "empty"):
-                _refuse("padding_mode", padding_mode, "reflect, wrap, symmetric and edge are built")
             print(f"Unsupported padding mode: {padding_mode}")
             raise RuntimeError(f"Unsupported padding mode: padding_mode={padding_mode!r}")
     else:
@@ -245,6 +261,13 @@ def make_params(in_dtype, flat=False, down_sample=None, down_sample_method="max"
     p = capi.PystripeParams()
     p.sigma1, p.sigma2, p.level = s1, s2, int(level)
     p.padding_mode = capi.PS_PADDING[mode]
+    if mode == "constant" and bleach_correction_clip_min is not None:
+        # the C side pads with log1p of this field also without a frequency (the clip is in log units already: the reference's double
+        # log, pystripe/core.py:1101-1105, is mirrored).  With a frequency the field is set below: NaN for a minimum estimated per tile
+        if not float(bleach_correction_clip_min) >= 0:
+            raise ValueError(f"bleach_correction_clip_min={bleach_correction_clip_min!r}: padding_mode='constant' pads with log1p of it; "
+                             "0 or more is expected")
+        p.bleach_clip_min = float(bleach_correction_clip_min)
     p.bidirectional = int(bool(bidirectional))
     if down_sample is not None:
         method = str(down_sample_method).lower()
@@ -826,7 +849,7 @@ def filter_streaks(img, sigma=(250, 250), level=0, wavelet="db9", crossover=10, 
     the reference (``raise_for_clips``).  With ``sigma=(0, 0)`` the correction runs alone."""
     _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, bleach_correction_clip_min=bleach_correction_clip_min,
                             bleach_correction_clip_med=bleach_correction_clip_med, bleach_correction_clip_max=bleach_correction_clip_max,
-                            enable_masking=enable_masking, threshold=threshold, sigma=sigma, extended=extended,
+                            enable_masking=enable_masking, threshold=threshold, sigma=sigma, extended=extended, padding_mode=padding_mode,
                             log1p_normalization_needed=log1p_normalization_needed))
     s1, s2 = _sigma_pair(_single_band(sigma, threshold))
     if s1 == s2 == 0 and bleach_correction_frequency is None:
@@ -856,7 +879,8 @@ def process_img(img, flat=None, gaussian_filter_2d=False, down_sample=None, down
     _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, bleach_correction_clip_min=bleach_correction_clip_min,
                             bleach_correction_clip_med=bleach_correction_clip_med, bleach_correction_clip_max=bleach_correction_clip_max,
                             exclude_dark_edges_set_them_to_zero=exclude_dark_edges_set_them_to_zero, threshold=threshold, sigma=sigma,
-                            new_size=new_size, extended=extended, log1p_normalization_needed=log1p_normalization_needed))
+                            new_size=new_size, extended=extended, padding_mode=padding_mode,
+                            log1p_normalization_needed=log1p_normalization_needed))
     sigma = _single_band(sigma, threshold)
     if new_size is not None:   # the values and the shapes, before anything touches the device
         shape = tuple(int(v) for v in img.shape[-2:])
@@ -979,7 +1003,7 @@ def batch_filter(input_path, output_path, files_list=None, workers=None, threads
         raise TypeError("convert_to_16bit and convert_to_8bit are both set: choose one output format")
     _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, bleach_correction_clip_min=bleach_correction_clip_min,
                             bleach_correction_clip_med=bleach_correction_clip_med, bleach_correction_clip_max=bleach_correction_clip_max,
-                            threshold=threshold, sigma=sigma, extended=extended))
+                            threshold=threshold, sigma=sigma, extended=extended, padding_mode=padding_mode))
     sigma = _single_band(sigma, threshold)
     if new_size is not None:   # the values, and the shapes where they are known, before anything touches the device
         new_size = check_new_size(new_size)
@@ -1194,8 +1218,8 @@ def _parse_args(argv=None):
     p.add_argument("--bleach_correction_max_method", action=argparse.BooleanOptionalAction, default=True,
                    help="bleach correction from the filtered row and column maxima (default) rather than from every filtered row")
     p.add_argument("--extended", action="store_true",
-                   help="batch_filter(extended=True): a bleach clip that is not given is estimated per tile, --down_sample_method median "
-                        "and --threshold are accepted")
+                   help="batch_filter(extended=True): a bleach clip that is not given is estimated per tile, --down_sample_method median, "
+                        "--threshold and the --padding_mode values constant, linear_ramp, maximum, mean, median and minimum are accepted")
     p.add_argument("--estimate_clips", action="store_true",
                    help="with --bleach_correction_frequency: take the clips that are not given from the slices of --input at 25 %%, 50 %% and "
                         "75 %% of the depth (four-class multi-Otsu of the log1p image, as process_images.py does) and print them")

@@ -20,7 +20,7 @@
  *
  * Not built (refused by the Python layer by name): masking, dark-edge
  * exclusion, biorthogonal wavelets and wavelets named without a table (the library holds the Daubechies family only; the
- * Python layer takes any other orthogonal wavelet as its coefficients), padding modes other than reflect / wrap / symmetric / edge.
+ * Python layer takes any other orthogonal wavelet as its coefficients), the padding mode 'empty'.
  * The lightsheet correction of process_img :1333-1348 is mi_lightsheet.h; the Python layer runs it between two
  * plans of this header, and so it does with the resize to new_size (:1356-1359), which is mi_tile_resize.h.
  *
@@ -54,6 +54,20 @@
  * the db9 kernels (18 taps unrolled, filters in scalar registers); mi_pystripe_plan_create_wavelet runs the kernels with a
  * run-time tap count (filter table in device memory, column passes staged in LDS), also when rec_lo holds the 18 db9 values.
  *
+ * Value padding (MI_PS_CONSTANT .. MI_PS_MINIMUM; filter_streaks :1088-1110, numpy.pad's semantics on the float32 log image L with
+ * the pad widths ((base_pad, base_pad + pad_y), (base_pad, base_pad + pad_x))): the padded image is written once per run and the first
+ * level reads it; reflect / wrap / symmetric / edge stay index maps and write none.  Axis 0 is padded first, then axis 1 over all rows:
+ *   maximum / minimum / mean / median  the pad rows hold the statistic of every column of L, the pad columns of a row that row's
+ *             statistic over its nx un-padded samples, so a corner holds the statistic of the column statistics.  The mean is
+ *             accumulated in float64; the median of an even count is the float32 mean of the two middle samples.  A line of up to
+ *             MI_PS_PAD_LDS_LINE samples is selected in LDS, a longer one by radix passes over global memory;
+ *   linear_ramp  from 0 at the outer edge: sample k of a front pad of width p is edge * k / p, sample k of a back pad of width p'
+ *             (counted from the tile) edge * (p' - 1 - k) / p'; axis 1 ramps the ramped pad rows;
+ *   constant  log1p(bleach_clip_min), also when bleach_frequency is 0 (the one case in which a clip is looked at without a
+ *             frequency; a zeroed field pads with 0): the clip is in log units and the reference takes the logarithm once more.  When
+ *             bleach_clip_min is estimated per tile (bleach_frequency > 0 and a NaN), log1p of that tile's estimate BEFORE it is
+ *             raised to log1p(1) -- mi_pystripe_plan_clips reports the raised one.  The struct has no field of its own for it.
+ *
  * A row (or maxima vector) of n samples stays in LDS as n + 12 doubles while n <= MI_PS_BLEACH_LDS_ROW; a longer one goes through
  * LDS in segments with the carried filter state and a float64 scratch row for the forward result.
  */
@@ -67,7 +81,12 @@ extern "C" {
 #endif
 
 typedef enum { MI_PS_U8 = 0, MI_PS_U16 = 1, MI_PS_F32 = 2 } mi_pystripe_dtype;
-typedef enum { MI_PS_REFLECT = 0, MI_PS_WRAP = 1, MI_PS_SYMMETRIC = 2, MI_PS_EDGE = 3 } mi_pystripe_padding;   /* numpy.pad modes */
+/* numpy.pad modes.  The first four are index maps (a padded sample is a copy of a source sample); the others are value modes: see
+ * "Value padding" above */
+typedef enum {
+    MI_PS_REFLECT = 0, MI_PS_WRAP = 1, MI_PS_SYMMETRIC = 2, MI_PS_EDGE = 3,
+    MI_PS_CONSTANT = 4, MI_PS_LINEAR_RAMP = 5, MI_PS_MAXIMUM = 6, MI_PS_MEAN = 7, MI_PS_MEDIAN = 8, MI_PS_MINIMUM = 9
+} mi_pystripe_padding;
 typedef enum { MI_PS_DOWN_MAX = 0, MI_PS_DOWN_MIN = 1, MI_PS_DOWN_MEAN = 2, MI_PS_DOWN_MEDIAN = 3 } mi_pystripe_down;
 #define MI_PS_MEDIAN_MAX_BLOCK 64   /* samples of a median block (down_y * down_x): they are sorted in registers */
 /* the clips estimated per tile (those given as NaN), as bits: what the Python layer reports as bleach_auto */
@@ -87,6 +106,10 @@ typedef enum {
 /* bleach correction: the longest row whose n + 12 doubles fit the LDS of one work-group beside the 16 wave totals of the scan:
  * (160 KiB - 16 * 16 B) / 8 B - 12 */
 #define MI_PS_BLEACH_LDS_ROW 20436
+/* median padding: the longest line whose keys stay in LDS beside the 256 digit counts and 16 control words of the selection.  A
+ * work-group takes a quarter of a CU's 160 KiB, so that four of them share a CU: 40 KiB / 4 B - 256 - 16.  (The notch kernel bounds a
+ * coefficient line to 8191 samples and with it a padded extent to 16365: a limit of all 160 KiB would never be passed.) */
+#define MI_PS_PAD_LDS_LINE 9968
 
 typedef struct {
     double sigma1, sigma2;     /* (0, 0): no stripe filter; both > 0 otherwise ("sigma must be positive", np_notch :654) */
@@ -109,7 +132,8 @@ typedef struct {
     int keep_uniform;          /* 1: no uniform-tile rule (filter_streaks called on its own filters a uniform tile like any other) */
     double bleach_frequency;   /* 0: no bleach correction; else butter's Wn, in (0, 1) (1: the Nyquist frequency) */
     double bleach_clip_min, bleach_clip_med, bleach_clip_max;   /* log1p units: 0 <= min < med < max; min is raised to log1p(1); a clip
-                                  that is NaN is estimated per tile ("Automatic clips" above) */
+                                  that is NaN is estimated per tile ("Automatic clips" above).  MI_PS_CONSTANT pads with log1p(bleach_clip_min),
+                                  with or without a frequency */
     int bleach_max_method;     /* 1: F is the outer product of the filtered row and column maxima of L */
 } mi_pystripe_params;
 

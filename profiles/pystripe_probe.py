@@ -11,6 +11,10 @@
                                                          tile, five runs of the median of 5 and their spread
     python profiles/pystripe_probe.py wavelet_trace K [B]  one warm-up and one run of choice K (0, 1, 2 in that order), batch B -- for
                                                          rocprofv3 --kernel-trace --stats, which gives the wavelet passes' share
+    python profiles/pystripe_probe.py padmodes [MODE ...]  sigma (250, 250), batch 16, one plan per padding mode (default: reflect and the six
+                                                         value modes): ms per tile by a host clock around 10 synchronised runs, seven
+                                                         such rounds: their median, least and largest.  One MODE under rocprofv3
+                                                         --kernel-trace --stats gives the share of the pad_* kernels
     python profiles/pystripe_probe.py e2e DIR [tiles]   `tiles` (default 256) deflate TIFF tiles of 2048 x 2048 uint16 under DIR/in,
                                                          then batch_filter -> DIR/out: tiles/s and the read / compute / write seconds
     python profiles/pystripe_probe.py cpu                the numpy / scipy restatement of tests/pystripe_util.py on one tile (context
@@ -142,6 +146,31 @@ def trace(b):
     plan.close()
 
 
+def padmodes(modes, rounds=7, reps=10, batch=16):
+    import torch
+    from ipp_amd import pystripe as ps
+    from tests import pystripe_util as U
+    dev = torch.device("cuda", 0)
+    x = torch.from_numpy(np.stack([U.synthetic_tile((NY, NX), 100 + i, np.uint16) for i in range(batch)])).to(dev)
+    for mode in modes:
+        plan = ps.Plan(dev, (NY, NX), np.uint16, ps.make_params(np.uint16, sigma=(250, 250), max_batch=batch, extended=True,
+                                                                **dict(PIPE, padding_mode=mode)))
+        out = plan.run(x)
+        for _ in range(3):
+            plan.run(x, out=out)
+        torch.cuda.synchronize(dev)
+        ms = []
+        for _ in range(rounds):
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                plan.run(x, out=out)
+            torch.cuda.synchronize(dev)
+            ms.append((time.perf_counter() - t0) / reps / batch * 1e3)
+        print(f"{mode:12s} batch {batch}: {np.median(ms):.4f} ms per tile ({rounds} rounds of {reps} runs: {min(ms):.4f} .. {max(ms):.4f}), "
+              f"scratch {plan.info.scratch_bytes_per_tile / 1e6:.0f} MB per tile", flush=True)
+        plan.close()
+
+
 def e2e(folder, n):
     import torch
     from ipp_amd import pystripe as ps
@@ -184,6 +213,8 @@ if __name__ == "__main__":
         wavelet_trace(int(sys.argv[2]), int(sys.argv[3]) if len(sys.argv) > 3 else 32)
     elif mode == "trace":
         trace(int(sys.argv[2]) if len(sys.argv) > 2 else 8)
+    elif mode == "padmodes":
+        padmodes(sys.argv[2:] or ["reflect", "constant", "linear_ramp", "maximum", "mean", "median", "minimum", "reflect"])
     elif mode == "e2e":
         e2e(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 256)
     elif mode == "cpu":
