@@ -34,7 +34,7 @@ CODES_U8, CODES_U16 = 0, 1   # mi_code_dtype (include/mi_thresholds.h)
 OTSU_OK, OTSU_TOO_FEW_VALUES, OTSU_VALUES_ARE_CLASSES = 0, 1, 2   # mi_otsu_status
 
 
-MI_ERR_INVALID, MI_ERR_HIP, MI_ERR_FFT, MI_ERR_NOMEM, MI_ERR_UNSUPPORTED = -1, -2, -3, -4, -5  # include/mi_common.h
+MI_ERR_INVALID, MI_ERR_HIP, MI_ERR_FFT, MI_ERR_NOMEM, MI_ERR_UNSUPPORTED, MI_ERR_INTERNAL = -1, -2, -3, -4, -5, -6  # include/mi_common.h
 
 
 class MiError(RuntimeError):
@@ -111,6 +111,11 @@ class LightsheetInfo(C.Structure):
         "ny", "nx", "ls_ny", "ls_nx", "ls_left_y", "ls_left_x", "bg_ny", "bg_nx", "bg_left_y", "bg_left_x", "bg_first_y0", "bg_first_y1", "bg_last_y0",
         "bg_last_y1", "bg_first_x0", "bg_first_x1", "bg_last_x0", "bg_last_x1", "max_window_samples", "ls_zero_last_row", "ls_zero_last_col",
         "bg_zero_last_row", "bg_zero_last_col", "integer_mode", "max_batch")] + [("scratch_bytes_per_tile", C.c_size_t)]
+
+
+class TileMaskInfo(C.Structure):
+    """mi_tile_mask_info (include/mi_tile_mask.h)."""
+    _fields_ = [("scratch_bytes", C.c_size_t), ("max_batch", C.c_int), ("fill_rounds", C.c_int)]
 
 
 ISO_MAX_STEPS = 32  # MI_ISO_MAX_STEPS
@@ -297,6 +302,11 @@ SIGNATURES = {
     "mi_tile_resize_plan_create": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "mi_tile_resize_run": (_i, [_vp, _vp, _vp, _vp, C.c_int64]),
     "mi_tile_resize_plan_destroy": (_i, [_vp]),
+    # mi_tile_mask.h
+    "mi_tile_mask_plan_create": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
+    "mi_tile_mask_run": (_i, [_vp, _vp, _vp, C.c_double, _i, _vp, _vp, C.c_int64]),
+    "mi_tile_mask_plan_info": (_i, [_vp, C.POINTER(TileMaskInfo)]),
+    "mi_tile_mask_plan_destroy": (_i, [_vp]),
     # mi_isodown.h
     "mi_isodown_derive": (_i, [_i, _i, C.c_double, C.c_double, C.c_double, _i, C.POINTER(IsodownInfo)]),
     "mi_isodown_plan_create": (_i, [_i, _i, _i, _i, C.POINTER(IsodownParams), C.POINTER(_vp)]),

@@ -34,8 +34,10 @@ Departures, all stated in INTEGRATION.md:
   * ``extended=True`` (``process_img``, ``filter_streaks``, ``batch_filter``, ``make_params``; default False) opens what these entry
     points refused by name before it existed and still refuse without it: a frequency without all three clips (the missing ones are
     then estimated per tile), ``down_sample_method='median'``, ``new_size`` in ``process_img``, a ``threshold``, the six value modes
-    of ``padding_mode``;
-  * refused by name also with it: ``enable_masking``, ``exclude_dark_edges_set_them_to_zero``,
+    of ``padding_mode``, ``enable_masking`` in ``filter_streaks`` (``get_img_mask``: threshold at ``bleach_correction_clip_med``, close,
+    open, corner flood fill; include/mi_tile_mask.h states the box window -- an even box moves content by one sample, as OpenCV's
+    documented formula does; agreement with cv2 itself is not verified);
+  * refused by name also with it: ``exclude_dark_edges_set_them_to_zero``,
     a ``new_size`` that needs skimage's Gaussian pre-filter (the tile
     shape below ``new_size`` as tuples with an axis that shrinks) or meets an integer tile with a float ``d_type``, ``.dcimg`` input,
     a median ``down_sample`` over blocks of more than 64 samples, a wavelet NAME without a built-in table (``'coif15'``: hand in
@@ -151,7 +153,7 @@ def _check_unsupported(kw):
         if kw.get("threshold") is not None:
             _refuse("threshold", kw["threshold"], "accepted with extended=True only (the thresholding dual-band path is not built)")
     for name in ("enable_masking", "exclude_dark_edges_set_them_to_zero"):
-        if kw.get(name):
+        if kw.get(name) and not (name == "enable_masking" and kw.get("extended")):
             _refuse(name, kw[name], "not built (needs OpenCV / scikit-image semantics)")
     threshold = kw.get("threshold")
     if threshold is not None and threshold <= 0 and "sigma" in kw:
@@ -711,6 +713,180 @@ def resize_tiles(img, new_size, device=None):
     return out if is_tensor else out.cpu().numpy()
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# foreground mask (pystripe/core.py:475-489; include/mi_tile_mask.h)
+
+def check_flood_fill_flag(flood_fill_flag):
+    """The connectivity cv2.floodFill reads from its flags (``flood_fill_flag & 0xff``): 4 or 8, or ValueError naming the argument."""
+    ok = isinstance(flood_fill_flag, (int, np.integer)) and not isinstance(flood_fill_flag, (bool, np.bool_))
+    if not ok or (int(flood_fill_flag) & 0xff) not in (4, 8):
+        raise ValueError(f"flood_fill_flag={flood_fill_flag!r}: its low byte is the connectivity, 4 or 8")
+    return int(flood_fill_flag) & 0xff
+
+
+def check_mask_steps(close_steps, open_steps):
+    """(close_steps, open_steps) as Python integers of 1 or more, or ValueError naming the one that is not."""
+    for name, k in (("close_steps", close_steps), ("open_steps", open_steps)):
+        if not isinstance(k, (int, np.integer)) or isinstance(k, (bool, np.bool_)) or k < 1:
+            raise ValueError(f"{name}={k!r}: the side of the box, an integer of 1 or more, is expected")
+    return int(close_steps), int(open_steps)
+
+
+def mask_code_bound(clip_med, ncodes):
+    """The code bound of the mask's threshold on an integer tile: the largest integer ``b`` (-1 .. ncodes - 1) with
+    ``code > b  <=>  log_table(ncodes)[code] > float32(clip_med)`` for every code, from the numpy log1p table that also decides the
+    bins of the automatic clips.  The table does not decrease, so the codes above the clip are a tail of it."""
+    from .thresholds import log_table
+    return int(np.searchsorted(log_table(int(ncodes)), np.float32(clip_med), side="right")) - 1
+
+
+class MaskPlan:
+    """mi_tile_mask plan for tiles of one shape and dtype.  ``run(tiles, threshold)``: [n, ny, nx] device tensor -> uint8 masks
+    [n, ny, nx] (0 / 1), and with ``masked=True`` also the tiles zeroed outside the mask (``masked`` may be a tensor to write to,
+    the input itself included).  ``fill_rounds`` is the number of fill rounds of the last run."""
+
+    def __init__(self, device, shape, dtype, close_steps=50, open_steps=500, connectivity=4, max_batch=0):
+        import torch
+        self.shape, self.dtype = (int(shape[0]), int(shape[1])), np.dtype(dtype)
+        code = _dtype_code(dtype, "dtype")
+        capi.require_gpu()
+        self.device = torch.device(device if device is not None else "cuda:0")
+        self._h = C.c_void_p()
+        capi.check(capi.lib().mi_tile_mask_plan_create(self.device.index or 0, self.shape[0], self.shape[1], code, int(close_steps), int(open_steps),
+                                                       int(connectivity), int(max_batch), C.byref(self._h)))
+
+    @property
+    def info(self):
+        info = capi.TileMaskInfo()
+        capi.check(capi.lib().mi_tile_mask_plan_info(self._h, C.byref(info)))
+        return info
+
+    @property
+    def fill_rounds(self):
+        return int(self.info.fill_rounds)
+
+    def run(self, tiles, threshold, log_domain=False, masked=None):
+        import torch
+        tdt = getattr(torch, self.dtype.name)
+        if not (isinstance(tiles, torch.Tensor) and tiles.is_cuda and tiles.is_contiguous() and tiles.dim() == 3 and tiles.dtype == tdt
+                and tuple(tiles.shape[1:]) == self.shape):
+            raise ValueError(f"MaskPlan.run: a contiguous [n, {self.shape[0]}, {self.shape[1]}] {self.dtype.name} device tensor is expected")
+        n = int(tiles.shape[0])
+        mask = torch.empty(tiles.shape, dtype=torch.uint8, device=tiles.device)
+        if masked is True:
+            masked = torch.empty_like(tiles)
+        elif masked is not None and (masked.shape != tiles.shape or masked.dtype != tdt or not masked.is_contiguous() or masked.device != tiles.device):
+            raise ValueError("MaskPlan.run: masked must look like the input")
+        with torch.cuda.device(tiles.device):
+            capi.check(capi.lib().mi_tile_mask_run(self._h, capi.current_stream_ptr(tiles.device), tiles.data_ptr(), float(threshold),
+                                                   int(bool(log_domain)), mask.data_ptr(), None if masked is None else masked.data_ptr(), n))
+        return mask if masked is None else (mask, masked)
+
+    def close(self):
+        if self._h:
+            capi.lib().mi_tile_mask_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_MASK_SCRATCH_BUDGET = 2 << 30   # device bytes one mask plan may own: sizes its batch
+
+
+def _mask_batch(n, shape):
+    """tiles of one round of a mask plan: at most 16, and as many as keep the plan's scratch (about 6 bytes per sample) in budget"""
+    return int(max(1, min(n, 16, _MASK_SCRATCH_BUDGET // (6 * shape[0] * shape[1] + 1))))
+
+
+def get_img_mask(img, threshold, close_steps=50, open_steps=500, flood_fill_flag=4, device=None):
+    """pystripe/core.py:475 on the GPU: ``img > threshold``, closed with a ``close_steps`` box, opened with an ``open_steps`` box, with
+    the background regions that hold a corner removed and every other hole filled (include/mi_tile_mask.h states the windows, the
+    border rule and the one-sample shift of an even box).  ``img``: a 2-D tile or a stack [n, ny, nx], numpy or device tensor, uint8 /
+    uint16 / float32; a bool mask in the same kind of container comes back.  Raw values are compared: no logarithm is taken."""
+    import torch
+    connectivity = check_flood_fill_flag(flood_fill_flag)
+    close_steps, open_steps = check_mask_steps(close_steps, open_steps)
+    if threshold != threshold:
+        raise ValueError(f"threshold={threshold!r}: a number is expected")
+    tiles, single, is_tensor, in_dtype = _as_stack(img, device)
+    shape = tuple(int(v) for v in tiles.shape[1:])
+    plan = MaskPlan(tiles.device, shape, in_dtype, close_steps, open_steps, connectivity, _mask_batch(int(tiles.shape[0]), shape))
+    try:
+        mask = plan.run(tiles, threshold).to(torch.bool)
+    finally:
+        plan.close()
+    mask = mask[0] if single else mask
+    return mask if is_tensor else mask.cpu().numpy()
+
+
+def _unmasked_clips(tiles, in_dtype, frequency, max_method, clips, verbose):
+    """float32 [n, 3]: the triple (min, med, max) of every tile with the clips that are None estimated from the tile as it is, as the
+    automatic-clip route of the plan reports them (``Plan.clips``; the given ones keep their slot).  Raises as ``raise_for_clips``."""
+    import torch
+    shape = tuple(int(v) for v in tiles.shape[1:])
+    # The plan's own route, also when no correction is asked for (the frequency is then a stand-in and the corrected image is dropped):
+    # the mask must be cut at exactly the median an un-masked run of the tile reports, and that one comes from the plan's kernels --
+    # numpy's log1p table for integer tiles, the device's log1pf and its two-pass histogram for float tiles.  threshold_multiotsu of a
+    # log image made by other arithmetic can put a float sample into the neighbouring bin and move the median by a bin.
+    if frequency is None:   # only the median is needed: estimate the whole triple, which is ordered by construction
+        clips = (None, None, None)
+    opts = dict(zip(BLEACH_CLIPS, clips))
+    prm = make_params(in_dtype, log_output=True, keep_uniform=True, max_batch=min(int(tiles.shape[0]), 16), extended=True,
+                      bleach_correction_frequency=0.5 if frequency is None else frequency, bleach_correction_max_method=max_method, **opts)
+    plan = Plan(tiles.device, shape, in_dtype, prm)
+    try:
+        plan.run(tiles)
+        torch.cuda.synchronize(tiles.device)
+        raise_for_clips(plan, verbose)
+        triples, _ = plan.clips()
+    finally:
+        plan.close()
+    return triples
+
+
+def _filter_streaks_masked(img, device, close_steps, open_steps, frequency, max_method, clips, verbose, **opts):
+    """filter_streaks with ``enable_masking``: the clips that are missing come from the un-masked tile, the mask from ``clip_med`` on
+    the log image, and the tile zeroed outside the mask (log1p(0) = 0, so this is ``log_image *= mask``) goes through the plan with
+    its clips given, never estimated again.  Tiles of a stack whose triples differ run one by one."""
+    import torch
+    tiles, single, is_tensor, in_dtype = _as_stack(img, device)
+    n, shape = int(tiles.shape[0]), tuple(int(v) for v in tiles.shape[1:])
+    need = clips[1] is None or (frequency is not None and any(c is None for c in clips))
+    if need:
+        triples = _unmasked_clips(tiles, in_dtype, frequency, max_method, clips, verbose)
+    else:
+        triples = np.tile(np.array([np.nan if c is None else c for c in clips], np.float32), (n, 1))
+    same = all(np.array_equal(triples[t], triples[0], equal_nan=True) for t in range(n))
+    groups = [list(range(n))] if same else [[t] for t in range(n)]
+    plan = MaskPlan(tiles.device, shape, in_dtype, close_steps, open_steps, 4, _mask_batch(1 if len(groups) > 1 else n, shape))
+    outs = []
+    try:
+        for group in groups:
+            lo, med, hi = (None if v != v else float(v) for v in triples[group[0]])
+            sub = tiles[group[0]:group[-1] + 1]
+            if med is None:   # a uniform tile has no estimate and no mask: it takes the plan's own route for uniform tiles
+                masked = sub
+            elif in_dtype.kind == "u":
+                _, masked = plan.run(sub, mask_code_bound(med, 256 if in_dtype == np.uint8 else 65536), False, masked=True)
+            else:
+                _, masked = plan.run(sub, float(np.float32(med)), True, masked=True)
+            if frequency is not None:
+                bleach = dict(bleach_correction_frequency=frequency, bleach_correction_max_method=max_method,
+                              bleach_correction_clip_min=lo, bleach_correction_clip_med=med, bleach_correction_clip_max=hi)
+            else:
+                bleach = {} if clips[0] is None else dict(bleach_correction_clip_min=clips[0])
+            outs.append(_run_tiles(masked, None, device, verbose=verbose, **opts, **bleach))
+    finally:
+        plan.close()
+    out = outs[0] if len(outs) == 1 else torch.cat(outs)
+    out = out[0] if single else out
+    return out if is_tensor else out.cpu().numpy()
+
+
 class Pipeline:
     """process_img for tiles of one shape and dtype: one pystripe plan, or -- with ``lightsheet`` (a dict of artifact_length,
     background_window_size, percentile, lightsheet_vs_background) or a ``new_size`` that differs from the tile's shape after
@@ -846,7 +1022,10 @@ def filter_streaks(img, sigma=(250, 250), level=0, wavelet="db9", crossover=10, 
     """pystripe/core.py:982 on the GPU.  ``crossover`` has no effect on this path (as in the reference).  ``log_output=True`` returns
     the float32 image just before ``expm1`` (an addition, for tests).  The bleach correction takes the three clips in log1p units; one
     left None is estimated per tile (``threshold_multiotsu(log1p(img), classes=4)``) and a tile it cannot be estimated for raises as in
-    the reference (``raise_for_clips``).  With ``sigma=(0, 0)`` the correction runs alone."""
+    the reference (``raise_for_clips``).  With ``sigma=(0, 0)`` the correction runs alone.  ``enable_masking`` (with ``extended=True``)
+    zeroes the log image outside ``get_img_mask(log image, bleach_correction_clip_med, close_steps, open_steps)`` before the filter, as
+    the reference does (:1079-1080); a clip that is missing is then estimated from the un-masked tile and handed to the plan
+    explicitly; with ``close_steps`` or ``open_steps`` None the run is the un-masked one."""
     _check_unsupported(dict(bleach_correction_frequency=bleach_correction_frequency, bleach_correction_clip_min=bleach_correction_clip_min,
                             bleach_correction_clip_med=bleach_correction_clip_med, bleach_correction_clip_max=bleach_correction_clip_max,
                             enable_masking=enable_masking, threshold=threshold, sigma=sigma, extended=extended, padding_mode=padding_mode,
@@ -857,6 +1036,18 @@ def filter_streaks(img, sigma=(250, 250), level=0, wavelet="db9", crossover=10, 
     wavelet = _early_wavelet((s1, s2), wavelet)
     bleach = _bleach_opts(img.shape, None, bleach_correction_frequency, bleach_correction_max_method, bleach_correction_clip_min,
                           bleach_correction_clip_med, bleach_correction_clip_max)
+    if enable_masking and close_steps is not None and open_steps is not None:
+        close_steps, open_steps = check_mask_steps(close_steps, open_steps)
+        if (bleach_correction_frequency is not None and bleach_correction_clip_min is None and (s1, s2) > (0, 0)
+                and str(padding_mode).lower() == "constant"):
+            _refuse("enable_masking", True, "padding_mode='constant' with an estimated bleach_correction_clip_min pads with the minimum before "
+                                            "it is raised to log1p(1), which the masked route does not carry: give bleach_correction_clip_min")
+        if bleach_correction_clip_med is not None and bleach_correction_clip_med != bleach_correction_clip_med:
+            raise ValueError(f"bleach_correction_clip_med={bleach_correction_clip_med!r}: the mask's threshold, a number, is expected")
+        return _filter_streaks_masked(img, device, close_steps, open_steps, bleach_correction_frequency, bleach_correction_max_method,
+                                      (bleach_correction_clip_min, bleach_correction_clip_med, bleach_correction_clip_max), verbose,
+                                      sigma=(s1, s2), level=level, wavelet=wavelet, padding_mode=padding_mode, bidirectional=bidirectional,
+                                      keep_uniform=True, log_output=log_output, extended=extended)
     return _run_tiles(img, None, device, sigma=(s1, s2), level=level, wavelet=wavelet, padding_mode=padding_mode, bidirectional=bidirectional,
                       keep_uniform=True, log_output=log_output, verbose=verbose, extended=extended, **bleach)
 

@@ -30,7 +30,8 @@ typedef enum {
     MI_ERR_HIP = -2,         /* a HIP runtime call failed */
     MI_ERR_FFT = -3,         /* a rocFFT call failed, or a rocFFT plan did not transform (every engine on that route checks itself once) */
     MI_ERR_NOMEM = -4,       /* workspace too small / allocation failed */
-    MI_ERR_UNSUPPORTED = -5  /* valid in the reference but not built here (e.g. NCC `enhance`) */
+    MI_ERR_UNSUPPORTED = -5, /* valid in the reference but not built here (e.g. NCC `enhance`) */
+    MI_ERR_INTERNAL = -6     /* a bound the library's own reasoning rules out was reached (e.g. the round cap of the mask's fill) */
 } mi_status;
 
 /* message of the last error raised on this thread ("" if none) */

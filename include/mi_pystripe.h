@@ -18,7 +18,10 @@
  * skimage.measure.block_reduce with numpy.median: blocks of up to MI_PS_MEDIAN_MAX_BLOCK samples, an even count gives the mean of the
  * two middle values; a NaN sorts by fminf / fmaxf, not as numpy sorts it.
  *
- * Not built (refused by the Python layer by name): masking, dark-edge
+ * The foreground mask of filter_streaks (enable_masking, get_img_mask :475-489) is mi_tile_mask.h; the Python layer runs it in front
+ * of a plan of this header, behind extended=True, and hands that plan the clips explicitly.  Its box window follows OpenCV's
+ * documented formula (an even box moves content by one sample); agreement with cv2 itself is not verified.
+ * Not built (refused by the Python layer by name): dark-edge
  * exclusion, biorthogonal wavelets and wavelets named without a table (the library holds the Daubechies family only; the
  * Python layer takes any other orthogonal wavelet as its coefficients), the padding mode 'empty'.
  * The lightsheet correction of process_img :1333-1348 is mi_lightsheet.h; the Python layer runs it between two
